@@ -140,7 +140,13 @@ def parse():
     p.add_argument("--config", choices=sorted(CONFIGS), default=None,
                    help="a BASELINE.json config by name (sets --num_frm / --token_kept_ratio / --max_new_tokens / --batch; flags given "
                         "explicitly on the command line still win): " + "; ".join(f"{k} = {v['what']}" for k, v in sorted(CONFIGS.items())))
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32): `ids` = the "
+                        "generated token ids of every clip of the job in clip order [clips, max_new_tokens]; same arguments = same inputs, so "
+                        "two builds can be compared output for output")
     args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     args.config_name = args.config or "cfg2"
     if args.config:
         given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
@@ -375,6 +381,33 @@ def gate_positions(n: int, lead: int, lead_next: int, margin: int):
     pos_in = lead - margin if lead - margin >= 0 else None
     pos_tail = max(n - (margin - lead_next), 0) if lead_next - margin < 0 else None
     return pos_in, pos_tail
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (integer values must be exact in it).  Arrays whose rows together
+    exceed `limit` bytes keep a fixed, seeded sample of rows (sorted; the row numbers go beside them as <name>_rows.npy, float64), so
+    that the same arguments always dump the same elements.  -> {file name: shape}"""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    share = limit // max(len(arrays), 1) - 2 * 4096            # room for two .npy headers per array
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "iub":
+            assert a.size == 0 or int(np.abs(a).max()) < (1 << 24), f"{name}: integers beyond 2^24 are not exact in float32"
+        a = a.astype(np.float32)
+        row_bytes = max(a[:1].nbytes, 1)
+        if a.nbytes > share:
+            keep = max(1, (share - 8 * a.shape[0]) // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            written[f"{name}_rows.npy"] = list(rows.shape)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[f"{name}.npy"] = list(a.shape)
+    return written
 
 
 def masked_steps_per_chunk(front_ms: float, step_ms: float, chunk_steps: int) -> int:
@@ -1043,6 +1076,8 @@ def main():
     job = parallel.merge_round_robin(per_rank_out, world * B) if use_dist else out
     assert all(c is not None and len(c) == N for c in job), "a clip of the job has no result after the gather"
     crc_per_clip = [zlib.crc32(np.asarray(c, dtype=np.int32).tobytes()) for c in job]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": np.asarray(job, dtype=np.int64)})
     per_rank_ms, gather_us = None, None
     if use_dist:
         # every rank's own clock around the same K steps (the line's time is their MAX), so that a slow rank or a slow link shows in

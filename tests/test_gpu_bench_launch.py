@@ -25,6 +25,15 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _need_a_gpu_per_rank(ranks: int):
+    """A node shared with other jobs caps how many processes may hold a GPU open at once; a run of `ranks` processes stays within it
+    only with one GPU per rank."""
+    import torch
+    n = torch.cuda.device_count()
+    if n < ranks:
+        pytest.skip(f"needs {ranks} GPUs (one per rank), found {n}")
+
+
 def _json_line(stdout: str) -> dict:
     lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, stdout[-2000:]
@@ -41,6 +50,21 @@ def test_single_process_line_has_the_contract_fields():
     assert d["rccl_ranks"] == 1 and d["dist_backend"] == "none"
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
+
+
+def test_dump_outputs_holds_the_last_timed_step_ids(tmp_path):
+    """--dump-outputs DIR: the ids of the last timed step, clip order, as float32 - the same ids the line's per-clip crcs describe."""
+    import zlib
+    import numpy as np
+    cmd = [sys.executable, "bench.py", "--gpus", "1"] + TINY + ["--steps", "3", "--no-instrument", "--dump-outputs", str(tmp_path)]     # last --steps wins
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["ids.npy"]
+    ids = np.load(tmp_path / "ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (4, 8)
+    assert [zlib.crc32(row.astype(np.int32).tobytes()) for row in ids] == d["ids_crc_per_clip"]
 
 
 @pytest.mark.parametrize("extra", [[], ["--pipeline"], ["--prefill-group", "2"]])
@@ -157,12 +181,14 @@ def test_config_presets_and_self_diagnosing_fields():
 
 
 def test_eight_rank_dry_run_of_the_configs3_command():
-    """`python bench.py --gpus 8 --config cfg4` IS BASELINE configs[3] (64 clips sharded 8-way).  No 8-GPU node has been available, so the
-    literal command runs here with tiny model dims and gloo: bench.py launches its own 8 ranks (8 processes sharing this box's GPU),
+    """`python bench.py --gpus 8 --config cfg4` IS BASELINE configs[3] (64 clips sharded 8-way).  The literal command runs with tiny model dims
+    and gloo: bench.py launches its own 8 ranks (8 processes, one per GPU),
     they rendezvous on 127.0.0.1, shard the 64 clips round-robin (clip i -> rank i % 8, lmms_eval/utils.py:675-681), time their steps
     on their own clocks, all_gather the ids every cycle and rank 0 merges them back into clip order (evaluator.py:519-546).
     The merged order is checked against an independent run: a single process that takes rank 3's shard (AURORA_BENCH_SHARD=3/8) must
-    produce exactly the ids the 8-rank job reports for clips 3, 11, 19, ..."""
+    produce exactly the ids the 8-rank job reports for clips 3, 11, 19, ...
+    Eight ranks are eight processes with a GPU open beside this one: the test runs where each rank has a GPU of its own."""
+    _need_a_gpu_per_rank(8)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["AURORA_DIST_BACKEND"] = "gloo"
     common = ["--config", "cfg4", "--tiny", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-power"]
@@ -195,8 +221,10 @@ def test_eight_full_rate_enqueue_loops_share_one_host():
     """on an 8-rank node the risk is the HOST - every rank's Python thread issues ~1.6e4 kernel launches and ~2.6e2
     hipGraph replays per cycle of 128 captions.  Rehearsal without the node: `--tiny-deep` keeps the REAL layer counts (31 ViT + 32 Llama
     layers, 128 slots, groups of 4, 256 tokens: the same launches per cycle as the metric's run) at tiny widths, so that eight such loops
-    run at full rate on this box's host (8 processes sharing its GPU, gloo).  The slowest rank's enqueue thread must need less than half
-    of the real cycle (9.0 s on one MI355X) of CPU per cycle - otherwise eight ranks on one host would be enqueue-bound."""
+    run at full rate on one host (8 processes, one per GPU, gloo).  The slowest rank's enqueue thread must need less than half
+    of the real cycle (9.0 s on one MI355X) of CPU per cycle - otherwise eight ranks on one host would be enqueue-bound.
+    Eight ranks are eight processes with a GPU open beside this one: the test runs where each rank has a GPU of its own."""
+    _need_a_gpu_per_rank(8)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["AURORA_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, "bench.py", "--gpus", "8", "--tiny-deep", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-power", "--no-instrument"]
