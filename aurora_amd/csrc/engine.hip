@@ -69,14 +69,11 @@ struct aur_ctx {
     float *w_metric, *w_mhat, *w_nmax, *w_sza, *w_szb;
     int32_t *w_nidx, *w_unm, *w_src, *w_dst;
     // workspace regions (llm)
-    half_t *l_xn, *l_qf, *l_attn, *l_h, *l_p1, *d_x, *d_q, *d_attn, *d_h, *d_scr;
-    unsigned long long *s_ssq_mlp, *s_ssq_attn;
-    float *d_logits, *d_part_o, *d_part_ml;
+    half_t *l_xn, *l_qf, *l_attn, *l_h, *l_p1, *d_q, *d_attn, *d_h, *d_scr;
+    float *d_part_o, *d_part_ml;
     float2* l_rope;
-    int32_t *s_pos, *s_ids, *s_len, *s_fin, *s_ptab;
-    int32_t* ptab_rw() { return const_cast<int32_t*>(ptab_cur); }
-    // generation state
-    int batch = 0, max_new = 0, eos = -1, nsplit = 1, pps = 1;
+    int32_t* s_ptab;                 // page tables of both banks
+    int nsplit = 1, pps = 1;
     int last_prefill_len = 0, mb_nseq = 1;                         // tuning knobs (aur_set_option)
     int decode_half = 0;             // 1: the next aur_llm_decode calls target a stream that owns half of the CUs (own hipGraph)
     int gemm_mode = 1, gemm_max_wgs = 0, gemm_tail_split = 1, prune_last = 1, gemm_nt_out = -1;                           // GEMM knobs: per ctx, copied into GemmArgs at every launch
@@ -87,23 +84,22 @@ struct aur_ctx {
     int attn_local = 1;                                                         // 1: workgroup-local join of the decode attention's splits where it applies (mk_dec_attn); 0 = always decode_attn_combine_kernel (A/B and test)
     int tome_fused_ln = 1;                                                      // 1: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge launch (bitwise norm_kernel's result; 0 = its own launch, A/B and test only)
     int fused_reduce = 0;                                                       // 1: the split-K reduce runs inside the projection kernel
-    hipGraphExec_t graph = nullptr, graph_h = nullptr;      // decode step: full grid / half grid (decode_half)
-    int graph_batch = 0;
-    // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graph) so
-    // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  The members above
-    // (d_x, s_*, d_logits, batch, max_new, eos, graph, ...) always alias the CURRENT bank (aur_select_bank).
+    // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graphs) so
+    // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  Every generation call
+    // acts on the CURRENT bank (aur_select_bank), reached through bank() only.
     struct Bank {
         half_t* d_x;
         unsigned long long *s_ssq_mlp, *s_ssq_attn;
         float* d_logits;
         int32_t *s_pos, *s_ids, *s_len, *s_fin;
-        const int32_t* ptab;
+        int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
         int batch = 0, max_new = 0, eos = -1;
-        hipGraphExec_t graph = nullptr, graph_h = nullptr;
+        hipGraphExec_t graph = nullptr, graph_h = nullptr;   // decode step: full grid / half grid (decode_half)
         int graph_batch = 0;
     } banks[2];
     int nbanks = 1, cur_bank = 0;
-    const int32_t* ptab_cur = nullptr;
+    Bank& bank() { return banks[cur_bank]; }
+    const Bank& bank() const { return banks[cur_bank]; }
     // caller-captured hipGraphs (aur_graph_begin / aur_graph_end / aur_graph_launch): a front end per shape bucket
     struct UserGraph {
         hipGraphExec_t exec = nullptr;
@@ -303,11 +299,6 @@ static int64_t carve(aur_ctx* c, char* base) {
     c->d_part_ml = k.take<float>(B * g.llm_heads * c->l_max_pages * 2);
     c->s_ptab = k.take<int32_t>(2 * (int64_t)c->kv_seqs * c->l_max_pages);
     for (int bk = 0; bk < 2; ++bk) c->banks[bk].ptab = c->s_ptab ? c->s_ptab + (int64_t)bk * c->kv_seqs * c->l_max_pages : nullptr;
-    {   // alias the current bank
-        const aur_ctx::Bank& K = c->banks[c->cur_bank];
-        c->d_x = K.d_x; c->s_ssq_mlp = K.s_ssq_mlp; c->s_ssq_attn = K.s_ssq_attn; c->d_logits = K.d_logits;
-        c->s_pos = K.s_pos; c->s_ids = K.s_ids; c->s_len = K.s_len; c->s_fin = K.s_fin; c->ptab_cur = K.ptab;
-    }
     return k.off;
 }
 
@@ -349,14 +340,15 @@ extern "C" int aur_create(const aur_config* cfg, aur_ctx** out) {
     return AUR_OK;
 }
 
+static void drop_graphs(aur_ctx::Bank& K) {
+    if (K.graph) (void)hipGraphExecDestroy(K.graph);
+    if (K.graph_h) (void)hipGraphExecDestroy(K.graph_h);
+    K.graph = K.graph_h = nullptr;
+}
+
 extern "C" void aur_destroy(aur_ctx* ctx) {
     if (!ctx) return;
-    ctx->banks[ctx->cur_bank].graph = ctx->graph;
-    ctx->banks[ctx->cur_bank].graph_h = ctx->graph_h;
-    for (auto& K : ctx->banks) {
-        if (K.graph) (void)hipGraphExecDestroy(K.graph);
-        if (K.graph_h) (void)hipGraphExecDestroy(K.graph_h);
-    }
+    for (auto& K : ctx->banks) drop_graphs(K);
     for (auto& ug : ctx->ugraphs)
         if (ug.exec) (void)hipGraphExecDestroy(ug.exec);
     for (auto& kv : ctx->timers) {
@@ -914,7 +906,7 @@ extern "C" int aur_project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, c
 static KvLayout llm_kv(const aur_ctx* c, int layer) {
     KvLayout L;
     L.base = (half_t*)c->kvpool + (int64_t)layer * c->l_layer_halves;
-    L.page_table = c->ptab_cur;
+    L.page_table = c->bank().ptab;
     L.max_pages = c->l_max_pages;
     L.page_tokens = c->cfg.page_tokens;
     L.heads = c->cfg.llm_heads;
@@ -925,12 +917,6 @@ static KvLayout llm_kv(const aur_ctx* c, int layer) {
     return L;
 }
 
-static void drop_graphs(aur_ctx* ctx) {
-    if (ctx->graph) (void)hipGraphExecDestroy(ctx->graph);
-    if (ctx->graph_h) (void)hipGraphExecDestroy(ctx->graph_h);
-    ctx->graph = ctx->graph_h = nullptr;
-}
-
 extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_tokens, int32_t eos_id, void* stream) {
     NO_CAPTURE("aur_begin_batch");
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_begin_batch: language weights not finalized");
@@ -938,22 +924,21 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     if (batch < 1 || batch > g.max_batch) return aur_fail(ctx, AUR_ERR_ARG, "batch %d outside [1, %d]", batch, g.max_batch);
     if (max_new_tokens < 1 || max_new_tokens > g.max_new_tokens) return aur_fail(ctx, AUR_ERR_ARG, "max_new_tokens %d outside [1, %d]", max_new_tokens, g.max_new_tokens);
     hipStream_t s = (hipStream_t)stream;
-    if ((ctx->graph || ctx->graph_h) && (ctx->max_new != max_new_tokens || ctx->eos != eos_id || ctx->graph_batch != batch)) {
+    aur_ctx::Bank& K = ctx->bank();
+    if ((K.graph || K.graph_h) && (K.max_new != max_new_tokens || K.eos != eos_id || K.graph_batch != batch)) {
         // eos / max_new / batch are by-value kernel arguments frozen inside the captured graph
         CK(hipStreamSynchronize(s));
-        drop_graphs(ctx);
+        drop_graphs(K);
     }
-    ctx->batch = batch;
-    ctx->max_new = max_new_tokens;
-    ctx->eos = eos_id;
-    CK(hipMemsetAsync(ctx->s_len, 0, (size_t)g.max_batch * 4, s));
-    CK(hipMemsetAsync(ctx->s_fin, 0, (size_t)g.max_batch * 4, s));
-    CK(hipMemsetAsync(ctx->s_pos, 0, (size_t)g.max_batch * 4, s));
-    CK(hipMemsetAsync(ctx->s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
+    K.batch = batch; K.max_new = max_new_tokens; K.eos = eos_id;
+    CK(hipMemsetAsync(K.s_len, 0, (size_t)g.max_batch * 4, s));
+    CK(hipMemsetAsync(K.s_fin, 0, (size_t)g.max_batch * 4, s));
+    CK(hipMemsetAsync(K.s_pos, 0, (size_t)g.max_batch * 4, s));
+    CK(hipMemsetAsync(K.s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
     const size_t bp = (size_t)rup(g.max_batch, 16);       // unused fragment lanes must hold finite values
-    CK(hipMemsetAsync(ctx->d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
-    CK(hipMemsetAsync(ctx->s_ssq_mlp, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
-    CK(hipMemsetAsync(ctx->s_ssq_attn, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
+    CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
+    CK(hipMemsetAsync(K.s_ssq_mlp, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
+    CK(hipMemsetAsync(K.s_ssq_attn, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
     return AUR_OK;
 }
 
@@ -961,13 +946,14 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
 // lm_head weights, 1/rms from s_ssq_mlp), then greedy bookkeeping + next-token embedding
 static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int set_pos, hipStream_t s) {
     const aur_config& g = ctx->cfg;
+    const aur_ctx::Bank& K = ctx->bank();
     SkinnyArgs h{};
-    h.xf = ctx->d_x; h.W = ctx->l_head_w; h.B = ctx->batch; h.Npad = ctx->l_vocab_pad; h.K = g.llm_hidden; h.n_real = g.llm_vocab;
-    h.mode = SK_LOGITS; h.out32 = ctx->d_logits; h.b_lo = b0; h.b_hi = b0 + nb; h.ssq_in = ctx->s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
+    h.xf = K.d_x; h.W = ctx->l_head_w; h.B = K.batch; h.Npad = ctx->l_vocab_pad; h.K = g.llm_hidden; h.n_real = g.llm_vocab;
+    h.mode = SK_LOGITS; h.out32 = K.d_logits; h.b_lo = b0; h.b_hi = b0 + nb; h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
     h.variant = ctx->skinny_variant;
     CK(launch_skinny(h, s));
-    CK(launch_argmax_advance(ctx->d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, ctx->eos, ctx->max_new, ctx->s_ids, ctx->s_len,
-                             ctx->s_fin, ctx->s_pos, ctx->d_x, ctx->s_ssq_mlp, advance, set_pos, s));
+    CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
+                             K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s));
     return AUR_OK;
 }
 
@@ -1079,8 +1065,9 @@ static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x
 static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who) {
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
     const aur_config& g = ctx->cfg;
-    if (ctx->batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
-    if (seq_len < 1 || seq_len + ctx->max_new > g.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, ctx->max_new, g.max_ctx);
+    const aur_ctx::Bank& K = ctx->bank();
+    if (K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
+    if (seq_len < 1 || seq_len + K.max_new > g.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, g.max_ctx);
     stage_begin(ctx, "prefill", s);
     ctx->last_prefill_len = seq_len;
     const int Mseq = rup(seq_len, 32);
@@ -1099,7 +1086,7 @@ static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds,
     const aur_config& g = ctx->cfg;
     const int d = g.llm_hidden, Mseq = rup(seq_len, 32);
     if (ctx->prof) kev_begin(ctx->kev[3], s);
-    CK(launch_xfrag_norm((half_t*)embeds + (int64_t)(seq_len - 1) * d, (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->d_x, ctx->s_ssq_mlp, s));
+    CK(launch_xfrag_norm((half_t*)embeds + (int64_t)(seq_len - 1) * d, (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->bank().d_x, ctx->bank().s_ssq_mlp, s));
     int rc = lm_head_and_advance(ctx, slot0, nseq, 0, seq_len, s);
     if (ctx->prof) kev_end(ctx->kev[3], s);       // closed on the error path too: the event ring and the roctx nesting stay balanced
     stage_end(ctx, stage, s);
@@ -1107,7 +1094,8 @@ static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds,
 }
 
 extern "C" int aur_llm_prefill_batch(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t seq_len, void* stream) {
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > ctx->batch) return aur_fail(ctx, AUR_ERR_ARG, "slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, ctx->batch);
+    const int B = ctx->bank().batch;
+    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = prefill_layers(ctx, slot0, nseq, embeds, seq_len, s, "aur_llm_prefill")) return rc;
     return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s);
@@ -1136,22 +1124,23 @@ __global__ void ptab_swap_kernel(int32_t* __restrict__ pt, int a0, int b0, int n
 }
 
 extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
-    if (!ctx->finalized || ctx->ll.empty() || ctx->batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_prefill_commit: no active batch");
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > ctx->batch) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slots [%d, %d) outside the batch of %d", slot0, slot0 + nseq, ctx->batch);
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_prefill_commit: no active batch");
+    if (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slots [%d, %d) outside the batch of %d", slot0, slot0 + nseq, K.batch);
     if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: KV sequences [%d, %d) outside [0, %d)", seq0, seq0 + nseq, ctx->kv_seqs);
     if (seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slot and sequence ranges overlap");
-    if (seq_len < 1 || seq_len + ctx->max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, ctx->max_new, ctx->cfg.max_ctx);
+    if (seq_len < 1 || seq_len + K.max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, ctx->cfg.max_ctx);
     hipStream_t s = (hipStream_t)stream;
     stage_begin(ctx, "prefill_commit", s);
     if (seq0 != slot0) {
         const int n = nseq * ctx->l_max_pages;
-        hipLaunchKernelGGL(ptab_swap_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ptab_rw(), slot0, seq0, nseq, ctx->l_max_pages);
+        hipLaunchKernelGGL(ptab_swap_kernel, dim3((n + 255) / 256), dim3(256), 0, s, K.ptab, slot0, seq0, nseq, ctx->l_max_pages);
         CK(hipGetLastError());
     }
-    CK(hipMemsetAsync(ctx->s_len + slot0, 0, (size_t)nseq * 4, s));
-    CK(hipMemsetAsync(ctx->s_fin + slot0, 0, (size_t)nseq * 4, s));
-    CK(hipMemsetAsync(ctx->s_pos + slot0, 0, (size_t)nseq * 4, s));
-    CK(hipMemsetAsync(ctx->s_ids + (int64_t)slot0 * ctx->max_new, 0, (size_t)nseq * ctx->max_new * 4, s));
+    CK(hipMemsetAsync(K.s_len + slot0, 0, (size_t)nseq * 4, s));
+    CK(hipMemsetAsync(K.s_fin + slot0, 0, (size_t)nseq * 4, s));
+    CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
+    CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
     return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit");
 }
 extern "C" int aur_llm_prefill(aur_ctx* ctx, int32_t slot, void* embeds, int32_t seq_len, void* stream) {
@@ -1161,19 +1150,20 @@ extern "C" int aur_llm_prefill(aur_ctx* ctx, int32_t slot, void* embeds, int32_t
 // ---- decode-step kernel argument builders (shared by the step and by aur_microbench)
 static SkinnyArgs mk_dec_qkv(aur_ctx* ctx, int l) {
     const aur_config& g = ctx->cfg;
+    const aur_ctx::Bank& K = ctx->bank();
     const int d = g.llm_hidden;
     SkinnyArgs q{};
-    q.ssq_in = ctx->s_ssq_mlp; q.norm_eps = g.llm_rms_eps; q.ssq_zero = ctx->s_ssq_attn;
-    q.xf = ctx->d_x; q.W = ctx->ll[l].qkv_w; q.B = ctx->batch; q.b_lo = 0; q.b_hi = ctx->batch; q.Npad = ctx->l_qkv_npad; q.K = d;
+    q.ssq_in = K.s_ssq_mlp; q.norm_eps = g.llm_rms_eps; q.ssq_zero = K.s_ssq_attn;
+    q.xf = K.d_x; q.W = ctx->ll[l].qkv_w; q.B = K.batch; q.b_lo = 0; q.b_hi = K.batch; q.Npad = ctx->l_qkv_npad; q.K = d;
     q.n_real = 3 * d; q.mode = SK_QKV; q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.qbuf = ctx->d_q; q.kv = llm_kv(ctx, l);
-    q.rope = ctx->l_rope; q.pos = ctx->s_pos; q.seq_ids = nullptr; q.variant = ctx->skinny_variant_wide;
+    q.rope = ctx->l_rope; q.pos = K.s_pos; q.seq_ids = nullptr; q.variant = ctx->skinny_variant_wide;
     q.half_grid = ctx->decode_half;
     return q;
 }
 static DecAttnArgs mk_dec_attn(aur_ctx* ctx, int l) {
     const aur_config& g = ctx->cfg;
     DecAttnArgs at{};
-    at.qbuf = ctx->d_q; at.kv = llm_kv(ctx, l); at.pos = ctx->s_pos; at.seq_ids = nullptr; at.B = ctx->batch; at.heads = g.llm_heads;
+    at.qbuf = ctx->d_q; at.kv = llm_kv(ctx, l); at.pos = ctx->bank().s_pos; at.seq_ids = nullptr; at.B = ctx->bank().batch; at.heads = g.llm_heads;
     at.hd = ctx->l_hd; at.nsplit = ctx->nsplit; at.pages_per_split = ctx->pps; at.scale = 1.0f / sqrtf((float)ctx->l_hd);
     at.part_o = ctx->d_part_o; at.part_ml = ctx->d_part_ml; at.out_f = ctx->d_attn; at.out_k32 = g.llm_hidden / 32;
     // engines whose capacity alone gives one attention workgroup per CU and still split the context (8-15 slots of 32 heads): the splits of a
@@ -1182,30 +1172,33 @@ static DecAttnArgs mk_dec_attn(aur_ctx* ctx, int l) {
     return at;
 }
 static SkinnyArgs mk_dec_o(aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
     const int d = ctx->cfg.llm_hidden;
     SkinnyArgs o{};
-    o.xf = ctx->d_attn; o.W = ctx->ll[l].o_w; o.B = ctx->batch; o.b_lo = 0; o.b_hi = ctx->batch; o.Npad = ctx->l_dpad; o.K = d; o.n_real = d;
-    o.mode = SK_ROW; o.xres = ctx->d_x; o.ssq_out = ctx->s_ssq_attn;
+    o.xf = ctx->d_attn; o.W = ctx->ll[l].o_w; o.B = K.batch; o.b_lo = 0; o.b_hi = K.batch; o.Npad = ctx->l_dpad; o.K = d; o.n_real = d;
+    o.mode = SK_ROW; o.xres = K.d_x; o.ssq_out = K.s_ssq_attn;
     o.variant = ctx->skinny_variant; o.part = (d >= ctx->row_split_min_k || ctx->cfg.max_batch > 64) ? ctx->d_part_row : nullptr;
     o.row_cnt = ctx->fused_reduce ? ctx->d_row_cnt : nullptr; o.half_grid = ctx->decode_half;
     return o;
 }
 static SkinnyArgs mk_dec_gateup(aur_ctx* ctx, int l) {
     const aur_config& g = ctx->cfg;
+    const aur_ctx::Bank& K = ctx->bank();
     const int d = g.llm_hidden;
     SkinnyArgs gu{};
-    gu.ssq_in = ctx->s_ssq_attn; gu.norm_eps = g.llm_rms_eps; gu.ssq_zero = ctx->s_ssq_mlp;
-    gu.xf = ctx->d_x; gu.W = ctx->ll[l].gateup_w; gu.B = ctx->batch; gu.b_lo = 0; gu.b_hi = ctx->batch; gu.Npad = ctx->l_gu_npad; gu.K = d;
+    gu.ssq_in = K.s_ssq_attn; gu.norm_eps = g.llm_rms_eps; gu.ssq_zero = K.s_ssq_mlp;
+    gu.xf = K.d_x; gu.W = ctx->ll[l].gateup_w; gu.B = K.batch; gu.b_lo = 0; gu.b_hi = K.batch; gu.Npad = ctx->l_gu_npad; gu.K = d;
     gu.n_real = 2 * g.llm_mlp; gu.mode = SK_SILU_MUL; gu.out_f = ctx->d_h; gu.out_k32 = g.llm_mlp / 32; gu.variant = ctx->skinny_variant_wide;
     gu.gu_ks = g.max_batch > 64 ? 1 : 2; gu.half_grid = ctx->decode_half;
     return gu;
 }
 static SkinnyArgs mk_dec_down(aur_ctx* ctx, int l) {
     const aur_config& g = ctx->cfg;
+    const aur_ctx::Bank& K = ctx->bank();
     const int d = g.llm_hidden;
     SkinnyArgs dn{};
-    dn.xf = ctx->d_h; dn.W = ctx->ll[l].down_w; dn.B = ctx->batch; dn.b_lo = 0; dn.b_hi = ctx->batch; dn.Npad = ctx->l_dpad; dn.K = g.llm_mlp;
-    dn.n_real = d; dn.mode = SK_ROW; dn.xres = ctx->d_x; dn.ssq_out = ctx->s_ssq_mlp;
+    dn.xf = ctx->d_h; dn.W = ctx->ll[l].down_w; dn.B = K.batch; dn.b_lo = 0; dn.b_hi = K.batch; dn.Npad = ctx->l_dpad; dn.K = g.llm_mlp;
+    dn.n_real = d; dn.mode = SK_ROW; dn.xres = K.d_x; dn.ssq_out = K.s_ssq_mlp;
     dn.variant = ctx->skinny_variant; dn.part = (g.llm_mlp >= ctx->row_split_min_k || g.max_batch > 64) ? ctx->d_part_row : nullptr;
     dn.row_cnt = ctx->fused_reduce ? ctx->d_row_cnt : nullptr; dn.half_grid = ctx->decode_half;
     return dn;
@@ -1223,16 +1216,16 @@ __global__ void stamp_kernel(unsigned long long* __restrict__ ring, int which) {
 
 static int enqueue_decode_step(aur_ctx* ctx, hipStream_t s, bool instrument) {
     const aur_config& g = ctx->cfg;
-    const int B = ctx->batch;
+    const int B = ctx->bank().batch;
     for (int l = 0; l < g.llm_layers; ++l) {
         CK(launch_skinny(mk_dec_qkv(ctx, l), s));
         {
             const DecAttnArgs at = mk_dec_attn(ctx, l);
             const bool stamp = l == ctx->stamp_layer && ctx->d_stamp && !instrument;
             if (instrument) kev_begin(ctx->kev[0], s);
-            if (stamp) hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, s, ctx->d_stamp, 0);
+            if (stamp) { hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, s, ctx->d_stamp, 0); CK(hipGetLastError()); }
             CK(launch_decode_attention_main(at, s));
-            if (stamp) hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, s, ctx->d_stamp, 1);
+            if (stamp) { hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, s, ctx->d_stamp, 1); CK(hipGetLastError()); }
             if (instrument) kev_end(ctx->kev[0], s);
             CK(launch_decode_attention_combine(at, s));
         }
@@ -1247,15 +1240,16 @@ static int enqueue_decode_step(aur_ctx* ctx, hipStream_t s, bool instrument) {
 }
 
 extern "C" int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream) {
-    if (!ctx->finalized || ctx->ll.empty() || ctx->batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_decode: call aur_begin_batch / aur_llm_prefill first");
+    aur_ctx::Bank& K = ctx->bank();
+    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_decode: call aur_begin_batch / aur_llm_prefill first");
     hipStream_t s = (hipStream_t)stream;
     if (steps <= 0) return AUR_OK;
     if (ctx->capturing) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_decode inside aur_graph_begin / aur_graph_end: the decode step replays its own graph");
     stage_begin(ctx, "decode", s);
     const bool use_graph = ctx->cfg.use_graph && !ctx->prof;
     if (use_graph) {
-        if (ctx->graph_batch != ctx->batch) drop_graphs(ctx);
-        hipGraphExec_t& gx = ctx->decode_half ? ctx->graph_h : ctx->graph;
+        if (K.graph_batch != K.batch) drop_graphs(K);
+        hipGraphExec_t& gx = ctx->decode_half ? K.graph_h : K.graph;
         if (!gx) {
             hipGraph_t gr;
             CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1265,7 +1259,7 @@ extern "C" int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream) {
             if (e != hipSuccess) return aur_fail(ctx, AUR_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
             CK(hipGraphInstantiate(&gx, gr, nullptr, nullptr, 0));
             (void)hipGraphDestroy(gr);
-            ctx->graph_batch = ctx->batch;
+            K.graph_batch = K.batch;
         }
         for (int i = 0; i < steps; ++i) CK(hipGraphLaunch(gx, s));
     } else {
@@ -1313,7 +1307,8 @@ extern "C" int aur_decode_stamps_read(aur_ctx* ctx, double* us_out, int32_t cap,
 // THIS stream from THIS thread (aur_vit_encode*, aur_project_splice, aur_llm_prefill_batch / _stage / _commit, aur_slot_reset /
 // _retire / _collect, the kernel-level entry points); calls that synchronise (aur_get_outputs, aur_unfinished, aur_slot_state,
 // aur_microbench, aur_decode_stamps_read, aur_set_option on a dec_* knob) and aur_llm_decode (it replays its own graph) are rejected by
-// the runtime and fail the capture.  Kernel arguments, including the ctx's gemm_* knobs, are frozen at capture time.
+// the runtime and fail the capture.  Kernel arguments, including the ctx's gemm_* knobs and the current bank, are frozen at capture
+// time: aur_select_bank is refused inside a capture.
 extern "C" int aur_graph_begin(aur_ctx* ctx, void* stream) {
     if (!ctx->finalized) return aur_fail(ctx, AUR_ERR_STATE, "aur_graph_begin: weights not finalized");
     if (ctx->capturing) return aur_fail(ctx, AUR_ERR_STATE, "aur_graph_begin: a capture is already open on this ctx");
@@ -1378,63 +1373,70 @@ extern "C" int aur_graph_destroy(aur_ctx* ctx, int32_t graph) {
 extern "C" int aur_get_outputs(aur_ctx* ctx, int32_t* ids_host, int32_t* lens_host, void* stream) {
     NO_CAPTURE("aur_get_outputs");
     hipStream_t s = (hipStream_t)stream;
-    if (ids_host) CK(hipMemcpyAsync(ids_host, ctx->s_ids, (size_t)ctx->batch * ctx->max_new * 4, hipMemcpyDeviceToHost, s));
-    if (lens_host) CK(hipMemcpyAsync(lens_host, ctx->s_len, (size_t)ctx->batch * 4, hipMemcpyDeviceToHost, s));
+    const aur_ctx::Bank& K = ctx->bank();
+    if (ids_host) CK(hipMemcpyAsync(ids_host, K.s_ids, (size_t)K.batch * K.max_new * 4, hipMemcpyDeviceToHost, s));
+    if (lens_host) CK(hipMemcpyAsync(lens_host, K.s_len, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
     return AUR_OK;
 }
 extern "C" int aur_unfinished(aur_ctx* ctx, int32_t* count_host, void* stream) {
     NO_CAPTURE("aur_unfinished");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> fin(ctx->batch), len(ctx->batch);
-    CK(hipMemcpyAsync(fin.data(), ctx->s_fin, (size_t)ctx->batch * 4, hipMemcpyDeviceToHost, s));
-    CK(hipMemcpyAsync(len.data(), ctx->s_len, (size_t)ctx->batch * 4, hipMemcpyDeviceToHost, s));
+    const aur_ctx::Bank& K = ctx->bank();
+    std::vector<int32_t> fin(K.batch), len(K.batch);
+    CK(hipMemcpyAsync(fin.data(), K.s_fin, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(len.data(), K.s_len, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
     int n = 0;
-    for (int b = 0; b < ctx->batch; ++b) n += (!fin[b] && len[b] < ctx->max_new) ? 1 : 0;
+    for (int b = 0; b < K.batch; ++b) n += (!fin[b] && len[b] < K.max_new) ? 1 : 0;
     *count_host = n;
     return AUR_OK;
 }
 // ---- per-slot control for continuous batching: slots of the active batch are independent sequences
 static int slot_check(aur_ctx* ctx, int32_t slot, const char* who) {
-    if (ctx->batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
-    if (slot < 0 || slot >= ctx->batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: slot %d outside the batch of %d", who, slot, ctx->batch);
+    const int batch = ctx->bank().batch;
+    if (batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
+    if (slot < 0 || slot >= batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: slot %d outside the batch of %d", who, slot, batch);
     return AUR_OK;
 }
 extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     if (int rc = slot_check(ctx, slot, "aur_slot_reset")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    CK(hipMemsetAsync(ctx->s_len + slot, 0, 4, s));
-    CK(hipMemsetAsync(ctx->s_fin + slot, 0, 4, s));
-    CK(hipMemsetAsync(ctx->s_pos + slot, 0, 4, s));
-    CK(hipMemsetAsync(ctx->s_ids + (int64_t)slot * ctx->max_new, 0, (size_t)ctx->max_new * 4, s));
+    const aur_ctx::Bank& K = ctx->bank();
+    CK(hipMemsetAsync(K.s_len + slot, 0, 4, s));
+    CK(hipMemsetAsync(K.s_fin + slot, 0, 4, s));
+    CK(hipMemsetAsync(K.s_pos + slot, 0, 4, s));
+    CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
     return AUR_OK;
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
     if (int rc = slot_check(ctx, slot, "aur_slot_retire")) return rc;
-    CK(hipMemsetD32Async((hipDeviceptr_t)(ctx->s_fin + slot), 1, 1, (hipStream_t)stream));      // a fill node: no host source, no synchronisation
+    CK(hipMemsetD32Async((hipDeviceptr_t)(ctx->bank().s_fin + slot), 1, 1, (hipStream_t)stream));      // a fill node: no host source, no synchronisation
     return AUR_OK;
 }
 extern "C" int aur_slot_state(aur_ctx* ctx, int32_t* lens_host, int32_t* finished_host, void* stream) {
     NO_CAPTURE("aur_slot_state");
-    if (ctx->batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_state: no active batch");
+    const aur_ctx::Bank& K = ctx->bank();
+    if (K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_state: no active batch");
     hipStream_t s = (hipStream_t)stream;
-    if (lens_host) CK(hipMemcpyAsync(lens_host, ctx->s_len, (size_t)ctx->batch * 4, hipMemcpyDeviceToHost, s));
-    if (finished_host) CK(hipMemcpyAsync(finished_host, ctx->s_fin, (size_t)ctx->batch * 4, hipMemcpyDeviceToHost, s));
+    if (lens_host) CK(hipMemcpyAsync(lens_host, K.s_len, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
+    if (finished_host) CK(hipMemcpyAsync(finished_host, K.s_fin, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
     CK(hipStreamSynchronize(s));
     return AUR_OK;
 }
 extern "C" int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_dev, int32_t* lens_dev, void* stream) {
     if (int rc = slot_check(ctx, slot0, "aur_slot_collect")) return rc;
-    if (nslots < 1 || slot0 + nslots > ctx->batch || !ids_dev || !lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_collect: slots [%d, %d) outside the batch of %d", slot0, slot0 + nslots, ctx->batch);
+    const aur_ctx::Bank& K = ctx->bank();
+    if (nslots < 1 || slot0 + nslots > K.batch || !ids_dev || !lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_collect: slots [%d, %d) outside the batch of %d", slot0, slot0 + nslots, K.batch);
     hipStream_t s = (hipStream_t)stream;
-    CK(hipMemcpyAsync(ids_dev, ctx->s_ids + (int64_t)slot0 * ctx->max_new, (size_t)nslots * ctx->max_new * 4, hipMemcpyDeviceToDevice, s));
-    CK(hipMemcpyAsync(lens_dev, ctx->s_len + slot0, (size_t)nslots * 4, hipMemcpyDeviceToDevice, s));
+    CK(hipMemcpyAsync(ids_dev, K.s_ids + (int64_t)slot0 * K.max_new, (size_t)nslots * K.max_new * 4, hipMemcpyDeviceToDevice, s));
+    CK(hipMemcpyAsync(lens_dev, K.s_len + slot0, (size_t)nslots * 4, hipMemcpyDeviceToDevice, s));
     return AUR_OK;
 }
 extern "C" int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream) {
-    if (ctx->batch < 1 || !dst_dev) return aur_fail(ctx, AUR_ERR_STATE, "aur_copy_logits: no active batch");
-    CK(hipMemcpyAsync(dst_dev, ctx->d_logits, (size_t)ctx->batch * ctx->cfg.llm_vocab * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const aur_ctx::Bank& K = ctx->bank();
+    if (K.batch < 1 || !dst_dev) return aur_fail(ctx, AUR_ERR_STATE, "aur_copy_logits: no active batch");
+    CK(hipMemcpyAsync(dst_dev, K.d_logits, (size_t)K.batch * ctx->cfg.llm_vocab * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return AUR_OK;
 }
 
@@ -1482,10 +1484,10 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
         ctx->decode_half = value ? 1 : 0;
         return AUR_OK;
     } else return aur_fail(ctx, AUR_ERR_ARG, "unknown option '%s'", name);
-    // kernel arguments are frozen in the captured graphs.  A graph may still be queued on a stream this call does not know: wait
-    // for the device before destroying it (tuning path only - nothing in the serving schedules changes these knobs)
-    if (ctx->graph || ctx->graph_h) (void)hipDeviceSynchronize();
-    drop_graphs(ctx);
+    // kernel arguments are frozen in the captured graphs of EVERY bank.  A graph may still be queued on a stream this call does not
+    // know: wait for the device before destroying it (tuning path only - nothing in the serving schedules changes these knobs)
+    if (ctx->banks[0].graph || ctx->banks[0].graph_h || ctx->banks[1].graph || ctx->banks[1].graph_h) (void)hipDeviceSynchronize();
+    for (auto& K : ctx->banks) drop_graphs(K);
     return AUR_OK;
 }
 
@@ -1494,7 +1496,8 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
 // bracketed by HIP events on `stream`.  Synchronises.  us_out = mean microseconds per launch.
 extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, double* us_out, void* stream) {
     NO_CAPTURE("aur_microbench");
-    if (!ctx->finalized || ctx->ll.empty() || ctx->batch < 1 || ctx->last_prefill_len < 1)
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1 || ctx->last_prefill_len < 1)
         return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: prefill a batch first");
     hipStream_t s = (hipStream_t)stream;
     const aur_config& g = ctx->cfg;
@@ -1511,9 +1514,9 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
         else if (!strcmp(kernel, "dec_down")) { CK(launch_skinny(mk_dec_down(ctx, l), s)); }
         else if (!strcmp(kernel, "dec_lm_head")) {
             SkinnyArgs h{};
-            h.ssq_in = ctx->s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
-            h.xf = ctx->d_x; h.W = ctx->l_head_w; h.B = ctx->batch; h.b_lo = 0; h.b_hi = ctx->batch; h.Npad = ctx->l_vocab_pad; h.K = d;
-            h.n_real = g.llm_vocab; h.mode = SK_LOGITS; h.out32 = ctx->d_logits; h.variant = ctx->skinny_variant;
+            h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
+            h.xf = K.d_x; h.W = ctx->l_head_w; h.B = K.batch; h.b_lo = 0; h.b_hi = K.batch; h.Npad = ctx->l_vocab_pad; h.K = d;
+            h.n_real = g.llm_vocab; h.mode = SK_LOGITS; h.out32 = K.d_logits; h.variant = ctx->skinny_variant;
             CK(launch_skinny(h, s));
         } else {
             int bit = !strcmp(kernel, "pre_norm") ? 1 : !strcmp(kernel, "pre_qkv") ? 2 : !strcmp(kernel, "pre_attn") ? 4 : !strcmp(kernel, "pre_o") ? 8
@@ -1540,12 +1543,7 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
 extern "C" int aur_select_bank(aur_ctx* ctx, int32_t bank) {
     if (bank < 0 || bank >= ctx->nbanks) return aur_fail(ctx, AUR_ERR_ARG, "bank %d outside [0, %d) (aur_config.num_banks)", bank, ctx->nbanks);
     if (!ctx->ws) return aur_fail(ctx, AUR_ERR_STATE, "aur_select_bank: workspace not set");
-    aur_ctx::Bank& o = ctx->banks[ctx->cur_bank];
-    o.batch = ctx->batch; o.max_new = ctx->max_new; o.eos = ctx->eos; o.graph = ctx->graph; o.graph_h = ctx->graph_h; o.graph_batch = ctx->graph_batch;
-    const aur_ctx::Bank& K = ctx->banks[bank];
+    if (ctx->capturing) return aur_fail(ctx, AUR_ERR_STATE, "aur_select_bank inside aur_graph_begin / aur_graph_end: the captured calls belong to bank %d", ctx->cur_bank);
     ctx->cur_bank = bank;
-    ctx->d_x = K.d_x; ctx->s_ssq_mlp = K.s_ssq_mlp; ctx->s_ssq_attn = K.s_ssq_attn; ctx->d_logits = K.d_logits;
-    ctx->s_pos = K.s_pos; ctx->s_ids = K.s_ids; ctx->s_len = K.s_len; ctx->s_fin = K.s_fin; ctx->ptab_cur = K.ptab;
-    ctx->batch = K.batch; ctx->max_new = K.max_new; ctx->eos = K.eos; ctx->graph = K.graph; ctx->graph_h = K.graph_h; ctx->graph_batch = K.graph_batch;
     return AUR_OK;
 }

@@ -10,6 +10,7 @@ exactly like `oracle/aurora_oracle.py` consumes them, so parity tests feed both 
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -46,6 +47,13 @@ def projector_settings(pc: dict, visual_hidden: Optional[int], llm_hidden: Optio
         if key in pc and have is not None and int(pc[key]) != int(have):
             raise ValueError(f"projector config {key} = {pc[key]} but the {'vision tower' if key[0] == 'v' else 'language model'} has hidden size {have}")
     return dict(depth=depth, hidden_act=act, bias=bias)
+
+
+@dataclass(frozen=True)
+class _BankState:
+    """Host view of one generation bank: the batch and max_new of its last accepted begin_batch."""
+    batch: int = 0
+    max_new: int = 0
 
 
 class AuroraCapEngine:
@@ -100,9 +108,9 @@ class AuroraCapEngine:
         self.proj_cfg = projector_settings(pc, vv["hidden_size"] if v else None, ll["hidden_size"] if l else None)
         c.proj_depth, c.proj_act = self.proj_cfg["depth"], _lib.ACT_BY_NAME[self.proj_cfg["hidden_act"]]
         self.spare_slots = spare_slots
-        self._front_graphs = {}                          # shape bucket -> FrontEndGraph (caption_stream's captured front ends), LRU order
+        self._front_graphs = {}                          # (bank, front-end CUs, shape bucket) -> caption_stream's FrontEndGraph, LRU order
         self.front_graph_cap = 16
-        self._bank_state = {0: (0, 0), 1: (0, 0)}        # bank -> (batch, max_new) for outputs()
+        self._banks = [_BankState(), _BankState()]       # the C side's current bank is self._bank
         self._bank = 0
         self.c = c
         self.v, self.l = v, l
@@ -398,15 +406,21 @@ class AuroraCapEngine:
 
     def select_bank(self, bank: int):
         """Switch the generation bank (double-buffered KV slots / state) that the following calls act on."""
-        self._bank_state[self._bank] = (getattr(self, "_batch", 0), getattr(self, "_max_new", 0))
         check(self.ctx, self.L.aur_select_bank(self.ctx, bank), "aur_select_bank")
         self._bank = bank
-        self._batch, self._max_new = self._bank_state[bank]
+
+    @property
+    def _batch(self) -> int:
+        return self._banks[self._bank].batch
+
+    @property
+    def _max_new(self) -> int:
+        return self._banks[self._bank].max_new
 
     def begin_batch(self, batch: int, max_new_tokens: int, eos_id: Optional[int]):
-        self._batch, self._max_new = batch, max_new_tokens
         check(self.ctx, self.L.aur_begin_batch(self.ctx, batch, max_new_tokens, -1 if eos_id is None else int(eos_id),
                                                self._stream()), "aur_begin_batch")
+        self._banks[self._bank] = _BankState(batch, max_new_tokens)
 
     def prefill(self, slot: int, embeds: torch.Tensor, seq_len: int):
         check(self.ctx, self.L.aur_llm_prefill(self.ctx, slot, embeds.data_ptr(), seq_len, self._stream()), "aur_llm_prefill")
@@ -603,10 +617,11 @@ class AuroraCapEngine:
                                        shared_cu_masked_stream(32 - front_cus, from_top=True, device=self.dev))
         return self._masked[front_cus]
 
-    def _front_end_replay(self, px: torch.Tensor, ids: List[int], r: int, seq: int):
+    def _front_end_replay(self, px: torch.Tensor, ids: List[int], r: int, seq: int, front_cus: int):
         """ViT + ToMe + projector / splice + staged prefill of ONE clip into KV sequence `seq` as a single hipGraph replay on torch's
-        current stream.  Graphs are captured per shape bucket - (frames, H, W, r, prompt structure, seq) - on first use and kept (at most
-        `front_graph_cap`, least recently used evicted): the per-bucket capture of the reference tree's serving engine
+        current stream.  Graphs are captured per bank (its page table is baked in), per `front_cus` (so is the persistent GEMM's grid)
+        and per shape bucket - (frames, H, W, r, prompt structure, seq) - on first use and kept (at most `front_graph_cap`, least
+        recently used evicted): the per-bucket capture of the reference tree's serving engine
         (src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279).  Returns (embeds, seq_len) for `prefill_commit`;
         `embeds` is the bucket's static buffer: the caller orders the next replay of the same bucket (same `seq`) after that commit."""
         if px.dim() != 4 or px.shape[1] != self.v.get("num_channels", 3):
@@ -619,7 +634,7 @@ class AuroraCapEngine:
         plan = self.splice_plan(ids, F, n_kept)
         if plan["seq_len"] < 1 or plan["seq_len"] + self._max_new > self.c.max_ctx:
             raise ValueError(f"prompt of {plan['seq_len']} positions + {self._max_new} new tokens exceeds max_ctx {self.c.max_ctx}")
-        key = (F, H, W, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
+        key = (self._bank, front_cus, F, H, W, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
         cache = self._front_graphs
         fg = cache.pop(key, None)
         if fg is None:
@@ -706,7 +721,7 @@ class AuroraCapEngine:
                                 sF.wait_event(reusable.pop(seq))
                             r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
                             if front_graph:
-                                emb, L = self._front_end_replay(px, list(ids), r, seq)      # one hipGraph replay per clip (captured per shape bucket)
+                                emb, L = self._front_end_replay(px, list(ids), r, seq, front_cus)      # one hipGraph replay per clip (captured per bucket)
                             else:
                                 vis = self.vit_encode(px, r)
                                 emb, L = self.project_splice(vis, list(ids))
@@ -876,6 +891,7 @@ class FrontEndGraph:
     The reference tree's own serving engine captures one graph per shape bucket and copies each request's inputs into the graph's
     static buffers before the replay (src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279); the bucket here is
     (group, frames, H, W, r, prompt structure, seq0), the static buffers are `pixels`, the three splice-plan arrays and `embeds`.
+    The graph writes through the page table of the bank current at construction: `launch` refuses to run in another bank.
     A front end is ~600 launches (31 ViT layers x 10 + 32 prefill layers x 8 + splices): replayed from the graph the host submits it
     in one call, so a serving loop can submit it just before the device can start it (bounded run-ahead: host-observed TTFT stays
     close to the device's) without starving the front-end stream.
@@ -888,6 +904,7 @@ class FrontEndGraph:
                  embeds: Optional[torch.Tensor] = None, prefill: str = "stage", slot0: int = 0):
         v, d = eng.v, eng.l["hidden_size"]
         self.eng, self.group, self.frames, self.r, self.seq0 = eng, group, frames, r, seq0
+        self.bank = eng._bank                                     # the graph writes through this bank's page table
         self.seq_len = plan["seq_len"]
         self.mseq = _rup(self.seq_len, 32)
         t0 = (height // v["patch_size"]) * (width // v["patch_size"]) + 1
@@ -945,6 +962,8 @@ class FrontEndGraph:
             self.text_rows.copy_(text_rows, non_blocking=True)
 
     def launch(self):
+        if self.eng._bank != self.bank:
+            raise ValueError(f"front end captured in bank {self.bank} launched in bank {self.eng._bank}")
         self.eng.graph_launch(self.gid)
 
     def close(self):

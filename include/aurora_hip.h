@@ -137,7 +137,8 @@ int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_tokens, int32_t
 /* Generation banks (num_banks = 2): each bank has its own max_batch KV slots, residual stream, outputs and captured
  * graph.  All generation calls (begin_batch / prefill / decode / get_outputs / ...) act on the selected bank, so batch
  * i can decode on one stream while batch i+1 is prefetched into the other bank on a second stream (decode is HBM-bound,
- * ViT + prefill are MFMA-bound).  The caller orders the streams with its own events. */
+ * ViT + prefill are MFMA-bound).  The caller orders the streams with its own events.  The current bank is part of what a
+ * caller-captured graph freezes (aur_graph_begin): AUR_ERR_STATE inside a capture. */
 int aur_select_bank(aur_ctx* ctx, int32_t bank);
 /* Prefill `slot` with embeds [round_up(seq_len,32), llm_hidden] (clobbered), write its KV pages, produce the
  * first token (argmax of the last position's logits). */
@@ -181,14 +182,15 @@ int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_d
  * aur_graph_begin opens a hipGraph capture on `stream` (thread-local mode); every enqueue-only call of this ctx that follows on that
  * stream from the same thread - aur_vit_encode(_hw), aur_project_splice, aur_llm_prefill / _batch / _stage / _commit, aur_slot_reset /
  * _retire / _collect, the kernel-level entry points - is recorded instead of run; aur_graph_end instantiates the recording and returns
- * a handle (>= 1) that aur_graph_launch replays with one call.  Pointers, shapes, KV sequence ids and the ctx's gemm_* knobs are frozen
- * at capture time: a serving loop keeps one graph per (frames, input size, r, prompt structure, target sequences) bucket and copies
- * each clip's pixels / ids into the bucket's staging buffers before the replay (aurora_amd/engine.py FrontEndGraph).  Calls that
- * synchronise or re-capture (aur_get_outputs, aur_unfinished, aur_slot_state, aur_microbench, aur_decode_stamps_read, aur_begin_batch,
- * aur_set_option, aur_finalize, aur_profile_enable) and aur_llm_decode (it replays its own graph) return AUR_ERR_STATE inside a capture
- * without touching the runtime: the capture stays valid, and aur_graph_end - which must be called in any case - closes it.  A
- * synchronising HIP call of the CALLER's own inside the capture invalidates it: aur_graph_end then returns AUR_ERR_HIP.  One capture at
- * a time per ctx.  aur_graph_destroy: the caller guarantees no replay is still queued. */
+ * a handle (>= 1) that aur_graph_launch replays with one call.  Pointers, shapes, KV sequence ids, the ctx's gemm_* knobs and the
+ * current bank (whose page table the prefill writes through) are frozen at capture time: a serving loop keeps one graph per (bank,
+ * frames, input size, r, prompt structure, target sequences) bucket and copies each clip's pixels / ids into the bucket's staging
+ * buffers before the replay (aurora_amd/engine.py FrontEndGraph).  Calls that synchronise or re-capture (aur_get_outputs,
+ * aur_unfinished, aur_slot_state, aur_microbench, aur_decode_stamps_read, aur_begin_batch, aur_set_option, aur_finalize,
+ * aur_profile_enable), aur_select_bank (it would split the capture between two banks) and aur_llm_decode (it replays its own graph)
+ * return AUR_ERR_STATE inside a capture without touching the runtime: the capture stays valid, and aur_graph_end - which must be called
+ * in any case - closes it.  A synchronising HIP call of the CALLER's own inside the capture invalidates it: aur_graph_end then returns
+ * AUR_ERR_HIP.  One capture at a time per ctx.  aur_graph_destroy: the caller guarantees no replay is still queued. */
 int aur_graph_begin(aur_ctx* ctx, void* stream);
 int aur_graph_end(aur_ctx* ctx, void* stream, int32_t* graph_out, int64_t* nodes_out);
 int aur_graph_launch(aur_ctx* ctx, int32_t graph, void* stream);
@@ -236,7 +238,7 @@ int aur_vit_layer(aur_ctx* ctx, int32_t layer, const void* x, const float* size,
 /* Copy the last-position logits of the most recent prefill / decode step into dst_dev: fp32 [batch, vocab]. */
 int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
 
-/* Tuning knobs.  Invalidate the captured decode graphs: "decode_fused_reduce" 0 (default: the split-K residual projections are followed
+/* Tuning knobs.  Invalidate the captured decode graphs (of every bank): "decode_fused_reduce" 0 (default: the split-K residual projections are followed
  * by a reduce launch) / 1 (the last-arriving split reduces inside the kernel; bitwise the same), "dec_attn_local" 1 (default: on engines
  * of 8-15 slots x 32 heads the splits of a (sequence, head) are the waves of one attention workgroup, joined through LDS) / 0
  * (decode_attn_combine_kernel joins them; bitwise the same), "dec_attn_pps" pages per decode-attention split, "skinny_row_split_min_k"

@@ -13,10 +13,10 @@ from tests.test_gpu_llm import LLM_CFGS
 pytestmark = pytest.mark.gpu
 
 
-def build(max_batch, spare, max_new=12):
+def build(max_batch, spare, max_new=12, num_banks=1):
     from aurora_amd.engine import AuroraCapEngine
     return AuroraCapEngine({"vit": VCFG, "llm": LLM_CFGS["hd32"]}, weights(), max_frames=6, max_batch=max_batch, max_ctx=512,
-                           max_new_tokens=max_new, spare_slots=spare)
+                           max_new_tokens=max_new, spare_slots=spare, num_banks=num_banks)
 
 
 def group_clips(n, frames, seed):
@@ -170,5 +170,28 @@ def test_caption_stream_replays_one_graph_per_shape_bucket():
         eng.front_graph_cap = 2                                    # eviction on nearly every clip: still the same ids
         assert dict(eng.caption_stream(cs, 0.5, 16, eos_id=None, check_every=4)) == eager
         assert len(eng._front_graphs) <= n_buckets
+    finally:
+        eng.close()
+
+
+def test_caption_stream_keeps_its_front_end_graphs_per_bank():
+    """A captured front end writes through the page table of the bank it was captured in: the overlapped stream run again in the
+    other bank must capture its own buckets (a replay of bank 0's graphs would stage bank 0's spare sequences and bank 1 would
+    commit pages nobody wrote), and a front end launched in the wrong bank is refused."""
+    from tests.test_gpu_caption_batch import clips
+    eng = build(3, 2, 16, num_banks=2)
+    try:
+        cs = clips(8, 23)
+        want = {i: eng.caption_ids(px, ids, 0.5, 16, eos_id=None) for i, (px, ids) in enumerate(cs)}
+        assert dict(eng.caption_stream(cs, 0.5, 16, eos_id=None, check_every=4)) == want
+        bank0 = dict(eng._front_graphs)
+        assert bank0 and all(k[0] == 0 and fg.bank == 0 for k, fg in bank0.items())
+        eng.select_bank(1)
+        assert dict(eng.caption_stream(cs, 0.5, 16, eos_id=None, check_every=4)) == want
+        bank1 = {k: fg for k, fg in eng._front_graphs.items() if k[0] == 1}
+        assert bank1 and all(fg.bank == 1 for fg in bank1.values())
+        assert not set(map(id, bank1.values())) & set(map(id, bank0.values()))
+        with pytest.raises(ValueError):
+            next(iter(bank0.values())).launch()                  # captured in bank 0, bank 1 is current
     finally:
         eng.close()

@@ -59,6 +59,66 @@ def test_two_banks_overlapped_streams_equal_sequential():
         eng.close()
 
 
+def two_bank_engine_and_reference():
+    """A two-bank engine, one batch of 3 prompts, and its ids decoded in bank 0 (39 steps after the prefill)."""
+    from aurora_amd.engine import AuroraCapEngine
+    from tests.util import rand_llm_weights
+    cfg = LLM_CFGS["hd64"]
+    gen = torch.Generator().manual_seed(43)
+    xs = [torch.randn(150, cfg["hidden_size"], generator=gen).half().float() for _ in range(3)]
+    eng = AuroraCapEngine({"vit": None, "llm": cfg}, {"llm": rand_llm_weights(cfg, 15)}, max_frames=1, max_batch=3, max_ctx=512,
+                          max_new_tokens=40, num_banks=2)
+
+    def run():                                                   # begin, prefill and decode the batch in the current bank
+        eng.begin_batch(3, 40, None)
+        eng.prefill_batch(0, 3, torch.cat([padded(e) for e in xs], 0).contiguous(), 150)
+        eng.decode(39)
+        return eng.outputs()
+    return eng, run, run()
+
+
+def test_a_knob_change_drops_the_decode_graph_of_every_bank():
+    """A graph-invalidating knob set while bank 0 is current must also drop the decode step bank 1 captured: bank 1's next
+    begin_batch has the same (batch, max_new, eos), so nothing else would re-capture it."""
+    eng, run, ref = two_bank_engine_and_reference()
+    try:
+        eng.select_bank(1)
+        assert run() == ref                                      # bank 1 captures its decode step
+        eng.select_bank(0)
+        eng.set_option("decode_stamp_layer", 0)
+        eng.select_bank(1)
+        before = eng.decode_stamps()[1]
+        assert run() == ref
+        assert eng.decode_stamps()[1] == before + 39             # the step replayed in bank 1 carries the stamps
+    finally:
+        eng.close()
+
+
+def test_select_bank_is_refused_inside_a_capture():
+    """The captured calls bake in the current bank's page table: a bank switch inside a capture is an error, not a silent split."""
+    from aurora_amd._lib import AuroraHipError
+    eng, run, ref = two_bank_engine_and_reference()
+    try:
+        with pytest.raises(AuroraHipError):
+            eng.graph_capture(lambda: eng.select_bank(1))
+        assert eng._bank == 0
+        torch.cuda.synchronize()
+        assert run() == ref
+    finally:
+        eng.close()
+
+
+def test_a_rejected_begin_batch_leaves_the_batch_in_place():
+    from aurora_amd._lib import AuroraHipError
+    eng, run, ref = two_bank_engine_and_reference()
+    try:
+        with pytest.raises(AuroraHipError):
+            eng.begin_batch(eng.max_batch + 1, 40, None)
+        assert eng.outputs() == ref                              # the previous batch's shape and ids
+    finally:
+        eng.close()
+
+
 def test_batch_of_52_four_column_groups_equals_single():
     """Up to 64 slots = four MFMA column groups in the decode GEMVs; ragged prompts, EOS stopping per slot."""
     cfg = LLM_CFGS["hd64"]
