@@ -14,9 +14,14 @@ Default schedule: steady-state continuous batching over `--batch` KV slots (128)
 batch / G groups (G = `--prefill-group`, 4) whose captions end group by group; the front end of a group's next clips (ViT + ToMe +
 splice + staged prefill into spare KV sequences) runs on its own stream restricted to 16 CUs of every XCD WHILE the slots decode
 (decode is HBM-bound, the front end MFMA-bound), and is committed into the group's slots at its boundary.  One step = one cycle of
-max_new_tokens - 1 decode steps = `batch` captions completed + `batch` front ends.  Every cycle's ids are checked against one
-batch-mode step.  `--overlap 0` runs the front ends between decode chunks on one stream (reported beside the line as
-`sequential_schedule`), `--batch-mode` times independent batches (`batch_mode`), `--pipeline` is round 1's two-bank variant.
+max_new_tokens - 1 decode steps = `batch` captions completed + `batch` front ends.  Every timed cycle's ids must be the same.
+`--overlap 0` runs the front ends between decode chunks on one stream, `--batch-mode` times independent batches, `--pipeline` is
+round 1's two-bank variant.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, `--dump-outputs` and the line.  `--full` adds
+the rest (minutes): a batch-mode reference step every cycle's ids are checked against (`batch_mode`), one cycle of the sequential
+schedule (`sequential_schedule`), the instrumented roofline pass, the one-slot and groups-of-2 operating points in child processes
+(`single_stream`, `frontier`), the CPU baseline and the latency of the ids gather; the `--no-*` flags switch parts of it off.
 
 For N > 1 clips shard across ranks (one process per GPU, no data-path collective); the only collective is the RCCL
 all_gather of the generated ids at the end of each step (the reference's gather_object, evaluator.py:519-546).
@@ -144,9 +149,17 @@ def parse():
                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32): `ids` = the "
                         "generated token ids of every clip of the job in clip order [clips, max_new_tokens]; same arguments = same inputs, so "
                         "two builds can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run and report everything beside the headline figure (minutes): the batch-mode reference step, the sequential "
+                        "cycle, the instrumented roofline pass, the child-process operating points, the CPU baseline and the gather latency; "
+                        "without it the --no-* flags above are all implied and --frontier is refused")
     args = p.parse_args()
     if args.steps < 1 or args.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        if args.frontier:
+            p.error("--frontier needs --full")
+        args.no_cpu_baseline = args.no_instrument = args.no_single_stream = args.no_latency_point = args.no_sequential_point = True
     args.config_name = args.config or "cfg2"
     if args.config:
         given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
@@ -339,7 +352,8 @@ def self_launch(n: int) -> int:
 def child_point(flags, timeout=1200):
     """One more operating point of this benchmark in a child process (its own engine); -> the child's JSON line, or None."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + list(flags) + ["--no-cpu-baseline", "--no-power", "--no-single-stream", "--no-latency-point", "--no-sequential-point"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + list(flags) + ["--no-cpu-baseline", "--no-power", "--no-single-stream", "--no-latency-point", "--no-sequential-point",
+                                                                       "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
         lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -608,11 +622,12 @@ def main():
         #      of G sequences) between two decode chunks.  One "step" = one cycle of N - 1 decode steps = B captions completed
         #      and B front ends run: exactly the work of one batch-mode step, but a clip's first token waits for its own
         #      group's front end only.  (What the reference harness does one clip at a time, evaluator.py:406-411.)
-        t_b = time.perf_counter()
-        batch_ref = step(True)                                     # one batch-mode step: reference captions + its timing
-        torch.cuda.synchronize()
-        batch_ms, batch_ttft = 1e3 * (time.perf_counter() - t_b), float(np.median(ttft_ms))
-        ttft_ms.clear()
+        if args.full:
+            t_b = time.perf_counter()
+            batch_ref = step(True)                                 # one batch-mode step: reference captions + its timing
+            torch.cuda.synchronize()
+            batch_ms, batch_ttft = 1e3 * (time.perf_counter() - t_b), float(np.median(ttft_ms))
+            ttft_ms.clear()
         offs = [g * S // NG for g in range(NG)]                    # refill instants of the groups inside a cycle of S steps
         ids_out = torch.zeros(NG, G, N, dtype=torch.int32, device=dev)
         len_out = torch.zeros(NG, G, dtype=torch.int32, device=dev)
@@ -974,8 +989,10 @@ def main():
             us_, tot_ = eng.decode_stamps()
             n_t = int(min(tot_ - stamps_before, len(us_)))
             stamps_timed = us_[len(us_) - n_t:] if n_t > 0 else None
-        # same clips in the same slots as the batch-mode step: batch-invariant kernels must give the same ids, every cycle
-        assert all(o == batch_ref for o in outs), "continuous batching produced different captions than the batch-mode step"
+        # same clips in the same slots every cycle (and as the batch-mode step with --full): batch-invariant kernels must give the same ids
+        ref = batch_ref if batch_ref is not None else outs[0]
+        assert all(o == ref for o in outs), ("continuous batching produced different captions than the batch-mode step" if batch_ref is not None
+                                             else "generated ids differ between identical cycles")
         if overlap and args.gemm_cus <= 0:
             eng.set_option("gemm_max_wgs", 0)                      # the instrumented pass below runs alone on the whole GPU
         ttft_ms.extend(a.elapsed_time(b) for a, b in lat_ev for _ in range(G))
@@ -998,7 +1015,7 @@ def main():
             poll_thread.join()
             start_thread.join()
             # the copied first ids are the captions' first ids (the read-back is real, not a timestamp of nothing)
-            assert all(int(first_host[g, j]) == batch_ref[g * G + j][0] for g in range(NG) for j in range(G)), "host read-back of the first tokens disagrees"
+            assert all(int(first_host[g, j]) == ref[g * G + j][0] for g in range(NG) for j in range(G)), "host read-back of the first tokens disagrees"
     elif not pipe:
         for _ in range(args.warmup):
             step()
@@ -1081,7 +1098,7 @@ def main():
     per_rank_ms, gather_us = None, None
     if use_dist:
         # every rank's own clock around the same K steps (the line's time is their MAX), so that a slow rank or a slow link shows in
-        # the record itself; and the cost of the one collective of the path, timed on its own after the steps
+        # the record itself; and (--full) the cost of the one collective of the path, timed on its own after the steps
         mine = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         allt = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allt, mine)
@@ -1093,13 +1110,14 @@ def main():
         allh = [torch.empty_like(mine_h) for _ in range(world)]
         dist.all_gather(allh, mine_h)
         host_enq["per_rank"] = [[float(x) for x in t.tolist()] for t in allh]
-        fence()
-        t_g = time.perf_counter()
-        for _ in range(5):
-            parallel.gather_results(out, N, B, cdev)
-        if cdev != "cpu":
-            torch.cuda.synchronize()
-        gather_us = 1e6 * (time.perf_counter() - t_g) / 5
+        if args.full:
+            fence()
+            t_g = time.perf_counter()
+            for _ in range(5):
+                parallel.gather_results(out, N, B, cdev)
+            if cdev != "cpu":
+                torch.cuda.synchronize()
+            gather_us = 1e6 * (time.perf_counter() - t_g) / 5
 
     result = None
     if rank == 0:
@@ -1193,7 +1211,7 @@ def main():
                                             "(median of %d); ideal = weights once + K / V of every cached token at 8 TB/s (SURVEY 8d)" % (N - 1, B, len(dec_ev))}
         if continuous and overlap:
             result["sequential_schedule"] = seq_sched
-        if continuous:
+        if continuous and batch_ref is not None:
             result["batch_mode"] = {"captions_per_s": B / (batch_ms / 1e3), "ms_per_step": batch_ms, "p50_ttft_ms": batch_ttft,
                                     "note": "one step of the non-continuous schedule (all %d front ends, then the %d-wide decode), same captions; "
                                             "host-timed around a single step after warm kernels" % (B, B)}
@@ -1204,7 +1222,7 @@ def main():
         if continuous and overlap and seq_sched:
             pts.append({"schedule": "sequential (front ends between decode chunks)", "prefill_group": G, "overlap": False,
                         "captions_per_s": seq_sched["captions_per_s"], "p50_ttft_ms": seq_sched["p50_ttft_ms"]})
-        if continuous:
+        if continuous and batch_ref is not None:
             pts.append({"schedule": "batch mode (all front ends, then the decode)", "prefill_group": G, "overlap": False,
                         "captions_per_s": B / (batch_ms / 1e3), "p50_ttft_ms": batch_ttft})
         result["frontier"] = pts

@@ -17,6 +17,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ["--tiny", "--batch", "4", "--num_frm", "2", "--max_new_tokens", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+FULL = ["--full"]          # the reference step, sequential cycle, instrumented pass and gather latency beside the timed steps
 
 
 def _free_port():
@@ -41,7 +42,7 @@ def _json_line(stdout: str) -> dict:
 
 
 def test_single_process_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + TINY, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + TINY + FULL, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -50,6 +51,22 @@ def test_single_process_line_has_the_contract_fields():
     assert d["rccl_ranks"] == 1 and d["dist_backend"] == "none"
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
+
+
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the default (overlapped, continuous) schedule sets up, warms up, times the steps and prints the line: no
+    batch-mode reference step, no sequential cycle, no instrumented pass."""
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--prefill-group", "2"] + TINY, cwd=ROOT, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "p50_ttft_ms", "ids_crc_per_clip"):
+        assert d.get(k) is not None, k
+    assert d["config"]["mode"].startswith("continuous batching") and "own stream" in d["config"]["mode"]
+    assert abs(d["value"] - 4 * 2 / (d["ms_per_step"] * 2 / 1e3)) < 1e-6 * d["value"]
+    assert d["sequential_schedule"] is None and "batch_mode" not in d and "decode_step" not in d
+    assert not any(k.startswith("roofline") for k in d) and "ttft_ms_single_clip" not in d and "cpu_baseline" not in d
+    assert [p["schedule"] for p in d["frontier"]] == ["this run (`value`)"]
 
 
 def test_dump_outputs_holds_the_last_timed_step_ids(tmp_path):
@@ -71,7 +88,7 @@ def test_dump_outputs_holds_the_last_timed_step_ids(tmp_path):
 def test_two_ranks_torchrun_gloo(extra):
     env = dict(os.environ, AURORA_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + TINY + extra
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + TINY + FULL + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _json_line(r.stdout)
@@ -103,7 +120,7 @@ def test_default_mode_is_steady_state_continuous_batching():
     """With >= 2 prefill groups the timed region is the steady-state continuous-batching loop (groups of --prefill-group clips
     collected and re-filled between decode chunks); its captions are verified inside bench.py against a batch-mode step, whose
     timing is reported beside it."""
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--prefill-group", "2"] + TINY, cwd=ROOT, capture_output=True,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--prefill-group", "2"] + TINY + FULL, cwd=ROOT, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -132,7 +149,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_gpus():
         pytest.skip("needs >= 2 GPUs on this node for an RCCL run")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "AURORA_DIST_BACKEND")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + TINY, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + TINY + FULL, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["dist_backend"] == "nccl" and d["rccl_ranks"] == 2 and d["value"] > 0
@@ -150,7 +167,7 @@ def test_one_rank_over_rccl_runs_every_collective_of_the_multi_rank_path(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "AURORA_DIST_BACKEND")}
     env.update(AURORA_DIST_FORCE="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "1"] + TINY + extra
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "1"] + TINY + FULL + extra
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _json_line(r.stdout)
@@ -169,7 +186,7 @@ def test_config_presets_and_self_diagnosing_fields():
     gather latency; the overlapped schedule reports a host-observed TTFT beside the device-event one."""
     env = dict(os.environ, AURORA_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--config", "cfg4", "--prefill-group", "2"] + TINY
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--config", "cfg4", "--prefill-group", "2"] + TINY + FULL
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _json_line(r.stdout)

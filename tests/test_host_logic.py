@@ -271,6 +271,22 @@ def test_bench_rejects_steps_below_one(monkeypatch):
     assert (a.steps, a.warmup, a.dump_outputs) == (3, 0, "out")
 
 
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """A plain run implies every --no-* flag of what --full adds; --full keeps them as given; --frontier only comes with --full."""
+    import sys as _sys
+    import bench
+    extras = ("no_cpu_baseline", "no_instrument", "no_single_stream", "no_latency_point", "no_sequential_point")
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in extras) and not a.frontier
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--full", "--no-instrument", "--frontier"])
+    a = bench.parse()
+    assert a.full and a.no_instrument and a.frontier and not any(getattr(a, k) for k in extras if k != "no_instrument")
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--frontier"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_rank_cpu_slices_are_disjoint_and_cover_the_numa_node():
     """Round 5 (VERDICT r4 next #7): ranks are bound to disjoint slices of the cores local to their GPU's NUMA node."""
     from aurora_amd.parallel import parse_cpulist, rank_cpu_slice
