@@ -243,3 +243,107 @@ def test_process_text_and_prompt():
     enc = lambda s, special: ([1] if special else []) + [100 + len(s)]
     ids = O.process_text(text, enc)
     assert ids == [1, 106, -200, 101, -200, 101, -200, 141]
+
+
+# ---------------------------------------------------------------------------------------------------
+# G17: trained-checkpoint statistics (tests/golden/make_golden_ckpt_stats.py).  The fixture is the yardstick of
+# tests/test_gpu_ckpt_stats.py - HF's own fp16 error against an fp64 evaluation - so what is pinned here is the yardstick itself:
+# the generators reproduce the hashed tensors, the oracle reproduces the fp64 logits, the yardstick is tight and finite, and the
+# cases leave the greedy-id comparison something to compare.
+# ---------------------------------------------------------------------------------------------------
+def _g17_sha(tensors):
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(np.ascontiguousarray(t.half().numpy()).tobytes())
+    return h.hexdigest()
+
+
+def _g17_llm_tensors(w):
+    out = [w["embed_tokens.weight"], w["norm.weight"], w["lm_head.weight"]]
+    for lw in w["layers"]:
+        out += [lw[k] for k in sorted(lw)]
+    return out
+
+
+def _g17_names():
+    from tests.util import ckpt_llm_cases
+    return [c[0] for c in ckpt_llm_cases()]
+
+
+def test_g17_covers_the_cases_of_the_issue():
+    from tests.util import CKPT_PREFIX_LENGTHS, ckpt_llm_cases
+    cases = {(s, g, e, T) for _, s, g, e, T in ckpt_llm_cases()}
+    assert tuple(CKPT_PREFIX_LENGTHS) == (40, 97, 300)
+    for seed in (0, 1):
+        for T in (40, 97, 300):
+            for gain, scales in ((1.0, (1.0, 2.0 ** -6, 2.0 ** -10, 2.0 ** 6)), (3.0, (1.0, 2.0 ** -6))):
+                for sc in scales:
+                    assert (seed, gain, sc, T) in cases
+    assert {(5, 8.0, 1.0, 300), (5, 8.0, 1.0, 97), (4, 8.0, 2.0 ** -6, 97)} <= cases    # the sharp-softmax cases that stay inside the cap
+    g = golden("g17_ckpt_stats.npz")
+    for name in _g17_names():
+        assert f"llm.{name}.logits" in g.files, name
+
+
+@pytest.mark.parametrize("name", _g17_names())
+def test_g17_generators_oracle_and_yardstick(name):
+    from tests.util import CKPT_LLM_CFG as cfg, CKPT_NEW_TOKENS, ckpt_like_llm_case, ckpt_llm_cases, ckpt_stored_rows
+    g = golden("g17_ckpt_stats.npz")
+    _, seed, gain, scale, T = next(c for c in ckpt_llm_cases() if c[0] == name)
+    p = f"llm.{name}."
+    w, emb = ckpt_like_llm_case(cfg, seed, gain, scale, T)
+    # every tensor fp16-representable, and the ones the fixture was made from
+    for t in _g17_llm_tensors(w) + [emb]:
+        assert torch.equal(t, t.half().float()) and torch.isfinite(t).all()
+    assert _g17_sha(_g17_llm_tensors(w)) == str(g[p + "sha_w"]), "ckpt_like_llm_weights drifted from the fixture (RNG?)"
+    assert _g17_sha([emb]) == str(g[p + "sha_x"]), "ckpt_like_embeds drifted from the fixture (RNG?)"
+    rows, ids, ref = g[p + "rows"].astype(np.int64), g[p + "ids"].astype(np.int64), tt(g[p + "logits"]).double()
+    lscale = float(g[p + "scale"])
+    assert list(rows) == ckpt_stored_rows(T) and len(ids) == CKPT_NEW_TOKENS
+    for k in ("logits", "margin", "hf32", "hf16", "scale"):
+        assert np.isfinite(g[p + k]).all(), k
+    assert g[p + "margin"].shape == g[p + "hf16"].shape == g[p + "hf32"].shape == (T + CKPT_NEW_TOKENS - 1,)
+    assert np.abs(g[p + "logits"]).max() <= lscale * (1 + 1e-6)                  # the scale is the maximum over ALL rows, stored or not
+    # the oracle in fp32 on these statistics: 1e-5 of the logit scale from the fp64 evaluation (measured ~1e-6)
+    full = torch.cat([emb, w["embed_tokens.weight"][tt(ids[:-1])]], 0)
+    h, _ = O.llama_forward(full, w, cfg, None, 0)
+    got = torch.nn.functional.linear(h, w["lm_head.weight"])
+    err = (got[rows].double() - ref).abs().max().item() / lscale
+    assert err <= 1e-5, err
+    top2 = got.double().topk(2, dim=1).values
+    np.testing.assert_allclose((top2[:, 0] - top2[:, 1]).numpy(), g[p + "margin"], atol=4e-5 * lscale)
+    for j in range(CKPT_NEW_TOKENS):                     # the ids are the fp64 greedy choice, reproduced wherever fp32 can tell
+        if g[p + "margin"][T - 1 + j] > 4e-5 * lscale:
+            assert int(got[T - 1 + j].argmax()) == ids[j], j
+    # HF in fp32 is the same function (so HF in fp16 is a yardstick for it), and the yardstick is inside its cap
+    assert float(g[p + "hf32"].max()) <= 1e-5, float(g[p + "hf32"].max())
+    worst16 = float(g[p + "hf16"].max())
+    assert float(g["cap"]) == 5e-3 and worst16 <= 5e-3, worst16
+    assert worst16 >= 2.0 ** -13                         # ... and is an fp16 error, not an accident of zeros
+    # the id comparison on the GPU is not vacuous: >= 90 % of the prefix rows have a margin above twice the case's HF-fp16 error
+    clear = int((g[p + "margin"][:T] > 2 * worst16 * lscale).sum())
+    assert clear >= 0.9 * T, (clear, T)
+
+
+@pytest.mark.parametrize("name", ["hd80_gelu", "hd16_quick"])
+def test_g17_vit_layer_generators_and_oracle(name):
+    from tests.util import CKPT_VIT_CASES, ckpt_like_vit_input, ckpt_like_vit_weights, rel_l2
+    g = golden("g17_ckpt_stats.npz")
+    cfg, frames, r, wseed, xseed = CKPT_VIT_CASES[name]
+    p = f"vit.{name}."
+    t = (cfg["image_size"] // cfg["patch_size"]) ** 2 + 1
+    lw = ckpt_like_vit_weights(cfg, wseed)["layers"][0]
+    x = ckpt_like_vit_input(xseed, frames, t, cfg["hidden_size"])
+    for v in list(lw.values()) + [x]:
+        assert torch.equal(v, v.half().float())
+    assert _g17_sha([lw[k] for k in sorted(lw)]) == str(g[p + "sha_w"])
+    assert _g17_sha([x]) == str(g[p + "sha_x"])
+    assert cfg["hidden_size"] // cfg["num_attention_heads"] in (80, 16)
+    match = dict(r=r, **{k: tt(g[p + k].astype(np.int64)) for k in ("unm_idx", "src_idx", "dst_idx")})
+    out, size = O.vit_layer(x, None, lw, cfg["num_attention_heads"], r, cfg["hidden_act"], forced_match=match)
+    assert rel_l2(out, tt(g[p + "out"])) <= 1e-5
+    np.testing.assert_array_equal(size[..., 0].numpy(), g[p + "size"])
+    assert "AuroraCLIPEncoderLayer" in str(g["vit_reference_module"])
+    r16, r32 = float(g[p + "ref16_rel_l2"]), float(g[p + "ref32_rel_l2"])
+    assert np.isfinite([r16, r32]).all() and r32 <= 1e-5 and 2.0 ** -13 <= r16 <= 5e-3, (r16, r32)
