@@ -64,12 +64,16 @@ SIGNATURES = {
     "aur_vit_pos_interp": (C.c_int, [_P, _I, _I, _P, _P]),
     "aur_vit_encode_hw": (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _P, _IP, _P]),
     "aur_project_splice": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "aur_project_splice_var": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "aur_begin_batch": (C.c_int, [_P, _I, _I, _I, _P]),
     "aur_select_bank": (C.c_int, [_P, _I]),
     "aur_llm_prefill": (C.c_int, [_P, _I, _P, _I, _P]),
     "aur_llm_prefill_batch": (C.c_int, [_P, _I, _I, _P, _I, _P]),
     "aur_llm_prefill_stage": (C.c_int, [_P, _I, _I, _P, _I, _P]),
     "aur_llm_prefill_commit": (C.c_int, [_P, _I, _I, _I, _P, _I, _P]),
+    "aur_llm_prefill_batch_var": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
+    "aur_llm_prefill_stage_var": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
+    "aur_llm_prefill_commit_var": (C.c_int, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "aur_llm_decode": (C.c_int, [_P, _I, _P]),
     "aur_get_outputs": (C.c_int, [_P, _IP, _IP, _P]),
     "aur_unfinished": (C.c_int, [_P, _IP, _P]),

@@ -42,6 +42,25 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
     const KvLayout& kv = a.kv;
     const int T16 = a.rows_per_seq >> 4, T32 = a.rows_per_seq >> 5;
     const int q0 = qb * 128 + w * 32;
+    // valid keys / queries and the position of query row 0: by value, or (a variable-length prefill) per sequence from device memory -
+    // one scalar load per workgroup, everything below is unchanged for a valid row
+    int t = a.t, q_pos0 = a.q_pos0;
+    int t_pad = 0x7fffffff;                         // query positions from here on are padding rows, stored as zeros (never, without lengths)
+    if (a.seq_lens) {
+        t = t_pad = var_len(a.seq_lens, seq, a.len_cap);
+        if (a.q_tail) q_pos0 = var_row0(t, a.rows_per_seq);
+        if (q_pos0 + qb * 128 >= t) {               // the whole query block is padding: nothing to compute, its output rows are zeros
+            const h4 z = h4{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+            for (int qt = 0; qt < 2; ++qt) {
+                const int query = q0 + qt * 16 + c;
+                if (query < a.rows_per_seq) {
+                    half_t* orow = a.O + ((int64_t)seq * a.rows_per_seq + query) * a.ldo + head * a.hd + 4 * g;
+                    for (int d = 0; d < VD16; ++d) *(h4*)(orow + d * 16) = z;
+                }
+            }
+            return;
+        }
+    }
 
     // Q fragments -> registers
     h8 qf[2][KBLK];
@@ -54,9 +73,9 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
             qf[qt][b] = *(const h8*)(a.Qf + ((((int64_t)seq * a.heads + head) * T16 + tq) * KBLK + b) * AUR_FRAG_HALVES + lane * 8);
     }
 
-    int nkb = (a.t + 63) >> 6;
+    int nkb = (t + 63) >> 6;
     if (a.causal) {
-        const int lastq = a.q_pos0 + qb * 128 + 127;
+        const int lastq = q_pos0 + qb * 128 + 127;
         const int lim = (lastq >> 6) + 1;
         nkb = nkb < lim ? nkb : lim;
     }
@@ -150,16 +169,16 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         __builtin_amdgcn_s_setprio(0);
         h8 pf[2][2];
         // wave-uniform: unless every key of this block is valid for every query of this wave, mask first (diagonal / last block)
-        if (!((kb * 64 + 63 < a.t) && (!a.causal || kb * 64 + 63 <= a.q_pos0 + q0))) {
+        if (!((kb * 64 + 63 < t) && (!a.causal || kb * 64 + 63 <= q_pos0 + q0))) {
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) {
-                const int query = a.q_pos0 + q0 + qt * 16 + c;
+                const int query = q_pos0 + q0 + qt * 16 + c;
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int key = kb * 64 + kt * 16 + 4 * g + i;
-                        const bool ok = key < a.t && (!a.causal || key <= query);
+                        const bool ok = key < t && (!a.causal || key <= query);
                         s[kt][qt][i] = ok ? s[kt][qt][i] : -INFINITY;
                     }
             }
@@ -222,6 +241,15 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         const int query = q0 + qt * 16 + c;
         if (query < a.rows_per_seq) {
             half_t* orow = a.O + ((int64_t)seq * a.rows_per_seq + query) * a.ldo + head * a.hd + 4 * g;
+            // a padding row of a variable-length prefill stays zero in every layer.  A branch of its own, not a select inside the
+            // conversion below: hipcc lowers `(half)(acc * inv)` per element either to v_fma_mixlo_f16 (one rounding) or to a multiply and
+            // a convert (two), and a select around it moved every element to the first form - the ViT's bits changed with it
+            if (q_pos0 + query >= t_pad) {
+                const h4 z = h4{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+#pragma unroll
+                for (int d = 0; d < VD16; ++d) *(h4*)(orow + d * 16) = z;
+                continue;
+            }
 #pragma unroll
             for (int d = 0; d < VD16; ++d) {
                 h4 o;

@@ -139,7 +139,21 @@ __device__ __forceinline__ int64_t vfrag_off(const KvLayout& L, int head, int d1
     return L.v_off + (((int64_t)head * L.vd16 + d16) * (L.page_tokens >> 5) + t32) * AUR_FRAG_HALVES;
 }
 
-#define HIP_CHECK_RET(expr)                                                     \
+// ---------------------------------------------------------------------------------------------
+// Variable-length prefill (aur_llm_prefill_*_var): the sequences of a pass lie `stride` rows apart and their lengths are read from
+// device memory by the kernels themselves.  The host never sees the lengths, so every reader clamps them into [1, cap = stride].
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int var_len(const int32_t* __restrict__ lens, int seq, int cap) {
+    const int t = lens[seq];
+    return t < 1 ? 1 : (t > cap ? cap : t);
+}
+// first row of the block of `lb` rows that ends at round_up(len, 32) (the pruned last prefill layer); 0 for a sequence shorter than that
+__device__ __forceinline__ int var_row0(int len, int lb) {
+    const int r = ((len + 31) & ~31) - lb;
+    return r > 0 ? r : 0;
+}
+
+#define HIP_CHECK_RET(expr)                                                    \
     do {                                                                        \
         hipError_t _e = (expr);                                                 \
         if (_e != hipSuccess) return aur_fail(ctx, AUR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \

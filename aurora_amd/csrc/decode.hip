@@ -900,7 +900,8 @@ hipError_t launch_skinny(const SkinnyArgs& a, hipStream_t s) {
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void xfrag_norm_kernel(const half_t* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                           float eps, int rows, int d, int b0, half_t* __restrict__ xf,
-                                                          unsigned long long* __restrict__ ssq_out) {
+                                                          unsigned long long* __restrict__ ssq_out,
+                                                          const int32_t* __restrict__ lens, int len_cap) {
     __shared__ float rs[16];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int grp = (b0 >> 4) + blockIdx.x;                 // 16-row group handled by this workgroup
@@ -910,7 +911,7 @@ __global__ __launch_bounds__(64 * NWV) void xfrag_norm_kernel(const half_t* __re
         const int row = b - b0;
         float ss = 0.f;
         if (row >= 0 && row < rows && (w || ssq_out)) {
-            const half_t* xr = x + row * ldx;
+            const half_t* xr = x + row * ldx + (lens ? (int64_t)(var_len(lens, row, len_cap) - 1) * d : 0);
             const int nchunk = d >> 3;
             for (int c0 = 0; c0 < nchunk; c0 += 512) {          // batches of 8 independent 16-byte loads per lane
                 h8 t[8];
@@ -940,7 +941,7 @@ __global__ __launch_bounds__(64 * NWV) void xfrag_norm_kernel(const half_t* __re
     const int b = grp * 16 + r, row = b - b0;
     const bool live = row >= 0 && row < rows;
     const float rstd = rs[r];
-    const half_t* xr = x + (live ? row : 0) * ldx + g * 8;
+    const half_t* xr = x + (live ? row : 0) * ldx + (lens ? (int64_t)(var_len(lens, live ? row : 0, len_cap) - 1) * d : 0) + g * 8;
     half_t* dst = xf + ((int64_t)grp * K32 * 64 + lane) * 8;
     for (int k0 = 0; k0 < K32; k0 += 8 * NWV) {                // batches of 8 tiles per wave: loads first, then math + stores
         h8 t[8];
@@ -966,12 +967,12 @@ __global__ __launch_bounds__(64 * NWV) void xfrag_norm_kernel(const half_t* __re
 }
 
 hipError_t launch_xfrag_norm(const half_t* x, int64_t ldx, const float* w, float eps, int rows, int d, int b0, half_t* xf,
-                             unsigned long long* ssq_out, hipStream_t s, int waves) {
+                             unsigned long long* ssq_out, hipStream_t s, int waves, const int32_t* lens, int len_cap) {
     if ((d & 31) || rows < 1) return hipErrorInvalidValue;
     const int g0 = b0 >> 4, g1 = (b0 + rows - 1) >> 4;
-    if (waves == 16) hipLaunchKernelGGL(xfrag_norm_kernel<16>, dim3(g1 - g0 + 1), dim3(1024), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out);
-    else if (waves == 8) hipLaunchKernelGGL(xfrag_norm_kernel<8>, dim3(g1 - g0 + 1), dim3(512), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out);
-    else hipLaunchKernelGGL(xfrag_norm_kernel<4>, dim3(g1 - g0 + 1), dim3(256), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out);
+    if (waves == 16) hipLaunchKernelGGL(xfrag_norm_kernel<16>, dim3(g1 - g0 + 1), dim3(1024), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out, lens, len_cap);
+    else if (waves == 8) hipLaunchKernelGGL(xfrag_norm_kernel<8>, dim3(g1 - g0 + 1), dim3(512), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out, lens, len_cap);
+    else hipLaunchKernelGGL(xfrag_norm_kernel<4>, dim3(g1 - g0 + 1), dim3(256), 0, s, x, ldx, w, eps, rows, d, b0, xf, ssq_out, lens, len_cap);
     return hipGetLastError();
 }
 
@@ -1266,7 +1267,8 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void argmax_advance_kernel(const fl
                                                              int32_t* __restrict__ out_ids, int32_t* __restrict__ out_len,
                                                              int32_t* __restrict__ finished, int32_t* __restrict__ pos,
                                                              half_t* __restrict__ xf, unsigned long long* __restrict__ ssq,
-                                                             int advance_pos, int set_pos) {
+                                                             int advance_pos, int set_pos, const int32_t* __restrict__ set_pos_lens,
+                                                             int len_cap) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int b = b0 + blockIdx.x, tid = threadIdx.x;
@@ -1309,7 +1311,8 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void argmax_advance_kernel(const fl
             }
             if (tok == eos_id || n + 1 >= max_new) finished[b] = 1;     // EOS, or the output row is full
         }
-        if (set_pos >= 0) pos[b] = set_pos;
+        if (set_pos_lens) pos[b] = var_len(set_pos_lens, blockIdx.x, len_cap);       // a variable-length prefill: each slot's own length
+        else if (set_pos >= 0) pos[b] = set_pos;
         // a finished (or idle) slot stops advancing: it keeps recomputing one position inside its own pages, so extra
         // decode steps (other slots still running, continuous batching) can never walk it past its KV allocation
         if (advance_pos && !was_finished) pos[b] += 1;
@@ -1334,8 +1337,9 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void argmax_advance_kernel(const fl
 
 hipError_t launch_argmax_advance(const float* logits, int b0, int nb, int vocab, const half_t* embed, int d, int eos_id,
                                  int max_new, int32_t* out_ids, int32_t* out_len, int32_t* finished, int32_t* pos,
-                                 half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s) {
+                                 half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s,
+                                 const int32_t* set_pos_lens, int len_cap) {
     hipLaunchKernelGGL(argmax_advance_kernel, dim3(nb), dim3(ARGMAX_THREADS), 0, s, logits, b0, vocab, embed, d, eos_id, max_new, out_ids,
-                       out_len, finished, pos, xf, ssq, advance_pos, set_pos);
+                       out_len, finished, pos, xf, ssq, advance_pos, set_pos, set_pos_lens, len_cap);
     return hipGetLastError();
 }

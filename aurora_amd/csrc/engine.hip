@@ -871,15 +871,15 @@ extern "C" int aur_rmsnorm(aur_ctx* ctx, const void* x, int32_t rows, int32_t d,
 }
 
 // ------------------------------------------------------------------------------------------ projector + splice
-extern "C" int aur_project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows, const int32_t* text_ids,
-                                  const int32_t* text_rows, int32_t ntext, int32_t seq_len, void* embeds, void* stream) {
-    if (!ctx->finalized || ctx->p_w.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_project_splice: projector weights not finalized");
+// seq_len < 0: the strided form (aur_project_splice_var) - `ntext` is the capacity of the text arrays, entries with text_rows < 0 are
+// skipped, and no padding row is cleared here (the variable-length prefill clears rows [len, stride) itself).
+static int project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows, const int32_t* text_ids,
+                          const int32_t* text_rows, int32_t ntext, int32_t seq_len, void* embeds, void* stream) {
     const aur_config& g = ctx->cfg;
-    if (seq_len < 1 || seq_len > g.max_ctx || nvis + ntext != seq_len) return aur_fail(ctx, AUR_ERR_ARG, "aur_project_splice: seq_len %d (nvis %d + ntext %d), max_ctx %d", seq_len, nvis, ntext, g.max_ctx);
     hipStream_t s = (hipStream_t)stream;
     stage_begin(ctx, "project", s);
     const int d = g.llm_hidden, lp = rup(seq_len, 32);
-    if (lp > seq_len) CK(hipMemsetAsync((half_t*)embeds + (int64_t)seq_len * d, 0, (size_t)(lp - seq_len) * d * 2, s));
+    if (seq_len > 0 && lp > seq_len) CK(hipMemsetAsync((half_t*)embeds + (int64_t)seq_len * d, 0, (size_t)(lp - seq_len) * d * 2, s));
     if (nvis > 0) {
         // modeling_projector.py:20-33: Linear, then (act, Linear) x (depth - 1); the activation rides in the producing GEMM's epilogue and
         // the LAST Linear writes straight into the spliced rows.  Intermediates ping-pong between l_p1 and l_xn (front-end scratch, free
@@ -900,6 +900,22 @@ extern "C" int aur_project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, c
     CK(launch_embed_rows(ctx->l_embed, d, text_ids, text_rows, ntext, (half_t*)embeds, d, s));   // utils.py:214-216
     stage_end(ctx, "project", s);
     return AUR_OK;
+}
+extern "C" int aur_project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows, const int32_t* text_ids,
+                                  const int32_t* text_rows, int32_t ntext, int32_t seq_len, void* embeds, void* stream) {
+    if (!ctx->finalized || ctx->p_w.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_project_splice: projector weights not finalized");
+    const aur_config& g = ctx->cfg;
+    if (seq_len < 1 || seq_len > g.max_ctx || nvis + ntext != seq_len) return aur_fail(ctx, AUR_ERR_ARG, "aur_project_splice: seq_len %d (nvis %d + ntext %d), max_ctx %d", seq_len, nvis, ntext, g.max_ctx);
+    return project_splice(ctx, vis, nvis, vis_rows, text_ids, text_rows, ntext, seq_len, embeds, stream);
+}
+extern "C" int aur_project_splice_var(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows, const int32_t* text_ids,
+                                      const int32_t* text_rows, int32_t ntext_cap, int32_t stride, void* embeds, void* stream) {
+    if (!ctx->finalized || ctx->p_w.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_project_splice_var: projector weights not finalized");
+    if (stride < 32 || stride % 32 || stride > ctx->l_ctx_pad)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_project_splice_var: stride %d is not a multiple of 32 within the %d positions of a sequence's KV pages", stride, ctx->l_ctx_pad);
+    if (nvis < 0 || ntext_cap < 0 || nvis > stride || ntext_cap > stride || !embeds || (nvis > 0 && (!vis || !vis_rows)) || (ntext_cap > 0 && (!text_ids || !text_rows)))
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_project_splice_var: nvis %d / ntext_cap %d outside [0, stride %d], or a null array", nvis, ntext_cap, stride);
+    return project_splice(ctx, vis, nvis, vis_rows, text_ids, text_rows, ntext_cap, -1, embeds, stream);
 }
 
 // ------------------------------------------------------------------------------------------ language model
@@ -944,7 +960,8 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
 
 // logits for batch columns [b0, b0 + nb) from the residual rows in d_x (x-fragment form; final RMSNorm folded into the
 // lm_head weights, 1/rms from s_ssq_mlp), then greedy bookkeeping + next-token embedding
-static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int set_pos, hipStream_t s) {
+static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int set_pos, hipStream_t s, const int32_t* set_pos_lens = nullptr,
+                               int len_cap = 0) {
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
     SkinnyArgs h{};
@@ -953,13 +970,15 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     h.variant = ctx->skinny_variant;
     CK(launch_skinny(h, s));
     CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
-                             K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s));
+                             K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
     return AUR_OK;
 }
 
 // One prefill layer; `which` selects the kernels (bit 0 norm1, 1 qkv, 2 attention, 3 o_proj, 4 norm2, 5 gate/up, 6 down)
 // so that aur_microbench can time each of them in isolation.
-static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, half_t* x, int seq_len, hipStream_t s) {
+// lens != nullptr (the _var entry points): `seq_len` is the row stride of the sequences, a multiple of 32, and sequence i holds
+// lens[i] rows (device memory, read by the attention kernel); the other kernels of a layer work row by row and need no length.
+static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr) {
     const aur_config& g = ctx->cfg;
     const LlmLayerW& w = ctx->ll[l];
     const int d = g.llm_hidden, Mseq = rup(seq_len, 32), M = nseq * Mseq;
@@ -975,6 +994,7 @@ static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, hal
         AttnArgs at{};
         at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = Mseq; at.t = seq_len;
         at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = ctx->l_attn; at.ldo = d; at.hd = ctx->l_hd;
+        at.seq_lens = lens; at.len_cap = Mseq;
         CK(launch_attention(at, s));
     }
     if (which & 8) {
@@ -1006,7 +1026,10 @@ static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, hal
 // and throws them away; every value that is kept is bit-identical here - a GEMM's per-element k order does not depend on M, the tile
 // kernels agree bitwise (tests), and the query block sees the same keys.  Saves 83 % of one layer of 32: ~2.5 % of a prefill.
 // Scratch: the compact [nseq * 128] activations live in l_h (free until this layer's gate/up), the compact Q fragments in l_qf.
-static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x, int seq_len, hipStream_t s) {
+// lens != nullptr: the block of sequence i is the 128 rows that end at rup(lens[i], 32) - row0 is per sequence, so the gathers and the
+// scatter are one small kernel that reads the lengths, and the query GEMM's RoPE position and the attention's q_pos0 derive from them
+// on the device (GemmArgs.tail_lens, AttnArgs.q_tail).  A sequence of <= 128 rows has row0 = 0: its block is the unpruned computation.
+static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr) {
     const aur_config& g = ctx->cfg;
     const LlmLayerW& w = ctx->ll[l];
     const int d = g.llm_hidden, mlp = g.llm_mlp, Mseq = rup(seq_len, 32), M = nseq * Mseq, LB = 128, Mc = nseq * LB, row0 = Mseq - LB;
@@ -1023,19 +1046,23 @@ static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x
         q.rope = ctx->l_rope; q.pos0 = 0; q.seq0 = slot; q.tag = GT_LLM_QKV;
         CK(ctx_gemm(ctx, q, EPI_QKV, s));
     }
-    CK(hipMemcpy2DAsync(xn_c, LB * rowb, ctx->l_xn + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
-    CK(hipMemcpy2DAsync(x_c, LB * rowb, x + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
+    if (lens) CK(launch_tail_rows(ctx->l_xn, x, xn_c, x_c, d, nseq, Mseq, LB, lens, 1, s));
+    else {
+        CK(hipMemcpy2DAsync(xn_c, LB * rowb, ctx->l_xn + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
+        CK(hipMemcpy2DAsync(x_c, LB * rowb, x + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
+    }
     {   // queries of the last block
         GemmArgs q{};
         q.A = xn_c; q.lda = d; q.W = w.qkv_w; q.M = Mc; q.Npad = d; q.K = d;
         q.rows_per_seq = LB; q.q_cols = d; q.k_cols = 0; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = row0; q.seq0 = slot; q.tag = GT_OTHER;
+        q.rope = ctx->l_rope; q.pos0 = row0; q.seq0 = slot; q.tag = GT_OTHER; q.tail_lens = lens; q.tail_cap = Mseq;
         CK(ctx_gemm(ctx, q, EPI_QKV, s));
     }
     {
         AttnArgs at{};
         at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = LB; at.t = seq_len;
         at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = attn_c; at.ldo = d; at.hd = ctx->l_hd; at.q_pos0 = row0;
+        at.seq_lens = lens; at.len_cap = Mseq; at.q_tail = 1;
         CK(launch_attention(at, s));
     }
     {
@@ -1057,37 +1084,54 @@ static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x
         dn.resid = x_c; dn.ldr = d; dn.n_real = d; dn.act = ACT_NONE; dn.tag = GT_OTHER;
         CK(ctx_gemm(ctx, dn, EPI_ROW, s));
     }
-    CK(hipMemcpy2DAsync(x + (int64_t)row0 * d, Mseq * rowb, x_c, LB * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
+    if (lens) CK(launch_tail_rows(nullptr, x, nullptr, x_c, d, nseq, Mseq, LB, lens, 0, s));
+    else CK(hipMemcpy2DAsync(x + (int64_t)row0 * d, Mseq * rowb, x_c, LB * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
+    return AUR_OK;
+}
+
+// ---- variable-length forms: sequences `stride` rows apart, lengths in device memory (never read here: enqueue-only, capturable)
+static int var_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds, int stride, const int32_t* lens) {
+    if (!embeds || !lens) return aur_fail(ctx, AUR_ERR_ARG, "%s: null %s", who, !embeds ? "embeds" : "seq_lens_dev");
+    if (stride < 32 || stride % 32) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d is not a positive multiple of 32", who, stride);
+    if (stride > ctx->l_ctx_pad) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d exceeds the %d positions of a sequence's KV pages", who, stride, ctx->l_ctx_pad);
+    if (nseq > ctx->cfg.max_batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: %d sequences exceed the front-end scratch of max_batch %d", who, nseq, ctx->cfg.max_batch);
     return AUR_OK;
 }
 
 // The layer stack of a prefill pass over KV sequences [seq0, seq0 + nseq): KV pages and front-end scratch only - no decode state.
-static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who) {
+// lens != nullptr: seq_len is the stride (checked by var_args) and the rows [lens[i], stride) of every sequence are cleared first: whatever
+// the caller left there, they are zeros in every layer (an all-zero row stays zero through norm, projections, RoPE and the MLP, and the
+// attention kernel stores zeros for it), and so are the K / V written for them.
+static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who, const int32_t* lens = nullptr) {
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
     if (K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
-    if (seq_len < 1 || seq_len + K.max_new > g.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, g.max_ctx);
+    if (!lens && (seq_len < 1 || seq_len + K.max_new > g.max_ctx)) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, g.max_ctx);
     stage_begin(ctx, "prefill", s);
     ctx->last_prefill_len = seq_len;
     const int Mseq = rup(seq_len, 32);
+    if (lens) CK(launch_clear_tail_rows((half_t*)embeds, g.llm_hidden, nseq, Mseq, lens, s));
     for (int l = 0; l < g.llm_layers; ++l) {
         // the compact scratch of the pruned last layer must fit l_h: nseq * 128 * (3 d + mlp) <= nseq * Mseq * mlp (and LB < Mseq)
         const bool prune = ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
-        int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s)
-                       : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s);
+        int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s, lens)
+                       : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s, lens);
         if (rc) return rc;
     }
     return AUR_OK;
 }
 // First tokens of slots [slot0, slot0 + nseq) from the last prompt rows of `embeds` (the final hidden states `prefill_layers` left
 // there): residual fragments + sum(x^2) - the lm_head applies the (folded) final RMSNorm itself -, logits, argmax, bookkeeping.
-static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* stage = "prefill") {
+static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* stage = "prefill",
+                                const int32_t* lens = nullptr) {
     const aur_config& g = ctx->cfg;
     const int d = g.llm_hidden, Mseq = rup(seq_len, 32);
     if (ctx->prof) kev_begin(ctx->kev[3], s);
-    CK(launch_xfrag_norm((half_t*)embeds + (int64_t)(seq_len - 1) * d, (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->bank().d_x, ctx->bank().s_ssq_mlp, s));
-    int rc = lm_head_and_advance(ctx, slot0, nseq, 0, seq_len, s);
+    // the last prompt row of every sequence and its decode position: seq_len - 1 / seq_len, or per sequence from the device lengths
+    CK(launch_xfrag_norm((half_t*)embeds + (lens ? 0 : (int64_t)(seq_len - 1) * d), (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->bank().d_x,
+                         ctx->bank().s_ssq_mlp, s, 16, lens, Mseq));
+    int rc = lm_head_and_advance(ctx, slot0, nseq, 0, seq_len, s, lens, Mseq);
     if (ctx->prof) kev_end(ctx->kev[3], s);       // closed on the error path too: the event ring and the roctx nesting stay balanced
     stage_end(ctx, stage, s);
     return rc;
@@ -1123,13 +1167,15 @@ __global__ void ptab_swap_kernel(int32_t* __restrict__ pt, int a0, int b0, int n
     *pb = t;
 }
 
-extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
+static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream, const int32_t* lens) {
     const aur_ctx::Bank& K = ctx->bank();
     if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_prefill_commit: no active batch");
     if (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slots [%d, %d) outside the batch of %d", slot0, slot0 + nseq, K.batch);
     if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: KV sequences [%d, %d) outside [0, %d)", seq0, seq0 + nseq, ctx->kv_seqs);
     if (seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slot and sequence ranges overlap");
-    if (seq_len < 1 || seq_len + K.max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, ctx->cfg.max_ctx);
+    if (lens) {
+        if (int rc = var_args(ctx, "aur_llm_prefill_commit_var", nseq, embeds, seq_len, lens)) return rc;
+    } else if (seq_len < 1 || seq_len + K.max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, ctx->cfg.max_ctx);
     hipStream_t s = (hipStream_t)stream;
     stage_begin(ctx, "prefill_commit", s);
     if (seq0 != slot0) {
@@ -1141,10 +1187,37 @@ extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq,
     CK(hipMemsetAsync(K.s_fin + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit");
+    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit", lens);
+}
+extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
+    return prefill_commit(ctx, slot0, nseq, seq0, embeds, seq_len, stream, nullptr);
+}
+extern "C" int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride,
+                                          const int32_t* seq_lens_dev, void* stream) {
+    if (!seq_lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit_var: null seq_lens_dev");
+    return prefill_commit(ctx, slot0, nseq, seq0, embeds, stride, stream, seq_lens_dev);
 }
 extern "C" int aur_llm_prefill(aur_ctx* ctx, int32_t slot, void* embeds, int32_t seq_len, void* stream) {
     return aur_llm_prefill_batch(ctx, slot, 1, embeds, seq_len, stream);
+}
+
+extern "C" int aur_llm_prefill_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev,
+                                         void* stream) {
+    const int B = ctx->bank().batch;
+    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
+    if (int rc = var_args(ctx, "aur_llm_prefill_batch_var", nseq, embeds, stride, seq_lens_dev)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = prefill_layers(ctx, slot0, nseq, embeds, stride, s, "aur_llm_prefill_batch_var", seq_lens_dev)) return rc;
+    return prefill_first_tokens(ctx, slot0, nseq, embeds, stride, s, "prefill", seq_lens_dev);
+}
+extern "C" int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev,
+                                         void* stream) {
+    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_stage_var: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", seq0, seq0 + nseq, ctx->kv_seqs);
+    if (int rc = var_args(ctx, "aur_llm_prefill_stage_var", nseq, embeds, stride, seq_lens_dev)) return rc;
+    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, (hipStream_t)stream, "aur_llm_prefill_stage_var", seq_lens_dev)) return rc;
+    stage_end(ctx, "prefill", (hipStream_t)stream);
+    return AUR_OK;
 }
 
 // ---- decode-step kernel argument builders (shared by the step and by aur_microbench)

@@ -57,15 +57,17 @@ __device__ __forceinline__ void qkv_epilogue_qk(const GemmArgs& a, f4 (&acc)[TN]
     // (rows_per_seq, pos0, the page size and mb are multiples of 16; M is a multiple of rows_per_seq): sequence, page and fragment row
     // are wave-uniform - scalar divisions, a scalar page-table load - and a lane adds only its own 16 bytes (lane * 8 halves).
     int tokb[TM];                                       // first token of the row block in its sequence (uniform)
+    int posb[TM];                                       // its position: pos0 + tokb, pos0 per sequence under a.tail_lens (uniform)
     int64_t row_off[TM];                                // halves from the Q buffer / the layer's page pool, without the (head, block) term (uniform)
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
         const int mrow = min(mb + u * 16, a.M - 16);   // row blocks past M: the last real block's entries are read, nothing is stored
         const int seq = mrow / a.rows_per_seq;
         tokb[u] = mrow - seq * a.rows_per_seq;
+        posb[u] = (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : a.pos0) + tokb[u];
         if (is_q) row_off[u] = (((int64_t)seq * kv.heads) * T16 + (tokb[u] >> 4)) * kv.kblk * AUR_FRAG_HALVES;
         else {
-            const int pos = a.pos0 + tokb[u];
+            const int pos = posb[u];
             const int64_t pid = kv.page_table ? (int64_t)kv.page_table[(int64_t)(a.seq0 + seq) * kv.max_pages + pos / kv.page_tokens] : (int64_t)(a.seq0 + seq);
             row_off[u] = pid * kv.page_halves + kfrag_off(kv, 0, (pos % kv.page_tokens) >> 4, 0);
         }
@@ -79,7 +81,7 @@ __device__ __forceinline__ void qkv_epilogue_qk(const GemmArgs& a, f4 (&acc)[TN]
             for (int p = 0; p < NP; ++p)
 #pragma unroll
                 for (int uu = 0; uu < UH; ++uu) {
-                    const f4* src = (const f4*)(a.rope + (int64_t)(a.pos0 + tokb[ph * UH + uu] + r) * (a.hd >> 1) + blk[p] * 16 + 4 * g);
+                    const f4* src = (const f4*)(a.rope + (int64_t)(posb[ph * UH + uu] + r) * (a.hd >> 1) + blk[p] * 16 + 4 * g);
                     cs[p][uu][0] = src[0];
                     cs[p][uu][1] = src[1];
                 }
@@ -151,16 +153,17 @@ __device__ __forceinline__ void qkv_epilogue_v(const GemmArgs& a, f4 (&acc)[TN][
 #pragma unroll
     for (int pu = 0; pu < TM / 2; ++pu) {
         const int mrow = min(mb + pu * 32, (a.M - 1) & ~31);          // row blocks past M: the last real block's page (nothing is stored)
-        tok_of[pu] = mrow % a.rows_per_seq;
-        pid[pu] = a.seq0 + mrow / a.rows_per_seq;
+        const int seq = mrow / a.rows_per_seq;
+        tok_of[pu] = (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : a.pos0) + mrow % a.rows_per_seq;   // position
+        pid[pu] = a.seq0 + seq;
     }
     if (kv.page_table) {
 #pragma unroll
-        for (int pu = 0; pu < TM / 2; ++pu) pid[pu] = kv.page_table[pid[pu] * kv.max_pages + (a.pos0 + tok_of[pu]) / kv.page_tokens];
+        for (int pu = 0; pu < TM / 2; ++pu) pid[pu] = kv.page_table[pid[pu] * kv.max_pages + tok_of[pu] / kv.page_tokens];
     }
 #pragma unroll
     for (int pu = 0; pu < TM / 2; ++pu) {
-        const int pos = a.pos0 + tok_of[pu];
+        const int pos = tok_of[pu];
         page_dst[pu] = mb + pu * 32 < a.M ? kv.base + pid[pu] * kv.page_halves + vfrag_off(kv, 0, 0, (pos % kv.page_tokens) >> 5) + (g * 16 + r) * 8 : nullptr;
     }
 #pragma unroll

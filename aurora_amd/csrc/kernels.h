@@ -28,6 +28,8 @@ struct GemmArgs {
     const float2* rope;     // [pos][hd/2] (cos, sin) or nullptr
     int pos0;               // position of row 0 of each sequence (multiple of 32)
     int seq0;               // first sequence's row in the page table
+    const int32_t* tail_lens;  // non-null (the pruned last layer of a variable-length prefill): sequence i's rows are the rows_per_seq rows that
+    int tail_cap;              // end at round_up(len_i, 32), so its pos0 is var_row0(var_len(tail_lens, i, tail_cap), rows_per_seq), not `pos0`
     // ---- per-ctx tuning knobs (aur_set_option; filled by the engine at every launch - nothing is process-global)
     int gemm_mode;          // 0: 128x128 kernel only, 1: auto, 2: force 256x256 when Npad % 256 == 0
     int max_wgs;            // 256x256 kernel: > 0 = at most this many persistent workgroups (= CUs); 0 = one per CU
@@ -74,6 +76,9 @@ struct AttnArgs {
     int nqb;                // filled by launch_attention: query blocks of 128 rows per sequence
     int q_pos0;             // position of query row 0 of every sequence among its keys (causal mask): 0 = the Q buffer starts at the
                             // sequence's first token; > 0 = it holds only a tail of the sequence (the pruned last prefill layer)
+    const int32_t* seq_lens;   // non-null: valid keys / queries of sequence i = var_len(seq_lens, i, len_cap) instead of `t` (device memory);
+    int len_cap;               // query rows at or beyond a sequence's length are stored as zeros
+    int q_tail;                // with seq_lens: 1 = q_pos0 of sequence i is var_row0(len_i, rows_per_seq) (the pruned last layer)
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
@@ -124,7 +129,13 @@ hipError_t launch_unpad_rows(const half_t* src, const float* size_src, int frame
 hipError_t launch_gather_rows(const half_t* src, int ld_src, const int32_t* rows, int nrows, int d, half_t* dst,
                               int ld_dst, hipStream_t s);
 hipError_t launch_embed_rows(const half_t* table, int d, const int32_t* ids, const int32_t* dst_rows, int n,
-                             half_t* dst, int ld_dst, hipStream_t s);
+                             half_t* dst, int ld_dst, hipStream_t s);      // dst_rows[i] < 0: entry i is skipped
+// variable-length prefill: rows [len_i, stride) of every sequence = 0
+hipError_t launch_clear_tail_rows(half_t* x, int d, int nseq, int stride, const int32_t* lens, hipStream_t s);
+// pruned last layer of a variable-length prefill: the block of `lb` rows that ends at round_up(len_i, 32) of every sequence, strided <-> compact.
+// gather: ca[i] = a[i][row0_i ..], cb[i] = b[i][row0_i ..]; scatter (gather == 0): b[i][row0_i ..] = cb[i]
+hipError_t launch_tail_rows(half_t* a, half_t* b, half_t* ca, half_t* cb, int d, int nseq, int stride, int lb, const int32_t* lens,
+                            int gather, hipStream_t s);
 
 // ---- decode.hip
 struct SkinnyArgs {
@@ -164,7 +175,8 @@ enum { SK_ROW = 0, SK_LOGITS = 1, SK_SILU_MUL = 2, SK_QKV = 3 };
 hipError_t launch_skinny(const SkinnyArgs& a, hipStream_t s);
 // xf[b0 + row] = RMSNorm(x[row]) (w != nullptr) or x[row], in x-fragment form; x rows are ldx halves apart
 hipError_t launch_xfrag_norm(const half_t* x, int64_t ldx, const float* w, float eps, int rows, int d, int b0, half_t* xf,
-                             unsigned long long* ssq_out, hipStream_t s, int waves = 16);
+                             unsigned long long* ssq_out, hipStream_t s, int waves = 16, const int32_t* lens = nullptr, int len_cap = 0);
+// lens != nullptr: row i is x[i * ldx + (var_len(lens, i, len_cap) - 1) * d ..] (the last prompt row of sequence i of a variable-length prefill)
 hipError_t launch_xfrag_pack(const half_t* x, int64_t ldx, int rows, int d, half_t* xf, hipStream_t s);
 
 struct DecAttnArgs {
@@ -187,4 +199,5 @@ hipError_t launch_decode_attention_combine(const DecAttnArgs& a, hipStream_t s);
 
 hipError_t launch_argmax_advance(const float* logits, int b0, int nb, int vocab, const half_t* embed, int d, int eos_id,
                                  int max_new, int32_t* out_ids, int32_t* out_len, int32_t* finished, int32_t* pos,
-                                 half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s);
+                                 half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s,
+                                 const int32_t* set_pos_lens = nullptr, int len_cap = 0);      // non-null: pos[b0 + i] = var_len(set_pos_lens, i, len_cap)

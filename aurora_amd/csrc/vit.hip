@@ -135,12 +135,13 @@ hipError_t launch_gather_rows(const half_t* src, int ld_src, const int32_t* rows
     return hipGetLastError();
 }
 
-// dst[dst_rows[i]][:] = table[ids[i]][:]
+// dst[dst_rows[i]][:] = table[ids[i]][:]   (dst_rows[i] < 0: unused entry of a padded plan, skipped)
 __global__ void embed_rows_kernel(const half_t* __restrict__ table, int d, const int32_t* __restrict__ ids,
                                   const int32_t* __restrict__ dst_rows, int n, half_t* __restrict__ dst, int ld_dst) {
     const int i = blockIdx.x;
     if (i >= n) return;
     const int id = ids[i], r = dst_rows ? dst_rows[i] : i;
+    if (r < 0) return;
     for (int c = threadIdx.x; c < (d >> 3); c += blockDim.x)
         *(h8*)(dst + (int64_t)r * ld_dst + c * 8) = *(const h8*)(table + (int64_t)id * d + c * 8);
 }
@@ -148,6 +149,44 @@ hipError_t launch_embed_rows(const half_t* table, int d, const int32_t* ids, con
                              half_t* dst, int ld_dst, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(128), 0, s, table, d, ids, dst_rows, n, dst, ld_dst);
+    return hipGetLastError();
+}
+
+// x[seq][len_seq .. stride) = 0: what a variable-length prefill does to its padding rows before the first layer
+__global__ void clear_tail_rows_kernel(half_t* __restrict__ x, int d, int stride, const int32_t* __restrict__ lens) {
+    const int seq = blockIdx.y, row = blockIdx.x;
+    if (row < var_len(lens, seq, stride)) return;
+    h8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (half_t)0.f;
+    half_t* dst = x + ((int64_t)seq * stride + row) * d;
+    for (int c = threadIdx.x; c < (d >> 3); c += blockDim.x) *(h8*)(dst + c * 8) = z;
+}
+hipError_t launch_clear_tail_rows(half_t* x, int d, int nseq, int stride, const int32_t* lens, hipStream_t s) {
+    hipLaunchKernelGGL(clear_tail_rows_kernel, dim3(stride, nseq), dim3(128), 0, s, x, d, stride, lens);
+    return hipGetLastError();
+}
+
+// rows [row0_seq, row0_seq + lb) of every sequence <-> compact [nseq][lb] blocks, row0_seq = var_row0(len_seq, lb)
+__global__ void tail_rows_kernel(half_t* __restrict__ a, half_t* __restrict__ b, half_t* __restrict__ ca, half_t* __restrict__ cb, int d,
+                                 int stride, int lb, const int32_t* __restrict__ lens, int gather) {
+    const int seq = blockIdx.y, i = blockIdx.x;
+    const int row = var_row0(var_len(lens, seq, stride), lb) + i;
+    if (row >= stride) return;                      // lb <= stride, so this cannot happen for a clamped length; kept as the bound of the store
+    const int64_t so = ((int64_t)seq * stride + row) * d, co = ((int64_t)seq * lb + i) * d;
+    for (int c = threadIdx.x; c < (d >> 3); c += blockDim.x) {
+        if (gather) {
+            *(h8*)(ca + co + c * 8) = *(const h8*)(a + so + c * 8);
+            *(h8*)(cb + co + c * 8) = *(const h8*)(b + so + c * 8);
+        } else {
+            *(h8*)(b + so + c * 8) = *(const h8*)(cb + co + c * 8);
+        }
+    }
+}
+hipError_t launch_tail_rows(half_t* a, half_t* b, half_t* ca, half_t* cb, int d, int nseq, int stride, int lb, const int32_t* lens,
+                            int gather, hipStream_t s) {
+    if (lb > stride) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tail_rows_kernel, dim3(lb, nseq), dim3(128), 0, s, a, b, ca, cb, d, stride, lb, lens, gather);
     return hipGetLastError();
 }
 

@@ -49,6 +49,88 @@ def projector_settings(pc: dict, visual_hidden: Optional[int], llm_hidden: Optio
     return dict(depth=depth, hidden_act=act, bias=bias)
 
 
+PROMPT_BUCKETS = (0, 32, 64, 128)
+
+
+def check_prompt_bucket(bucket: int) -> int:
+    """0 = every prompt is laid out at its exact length; 32 / 64 / 128 = at the next multiple of the bucket (`prompt_stride`)."""
+    if bucket not in PROMPT_BUCKETS:
+        raise ValueError(f"prompt_bucket {bucket!r} is not one of {PROMPT_BUCKETS}")
+    return int(bucket)
+
+
+def prompt_stride(seq_len: int, bucket: int) -> int:
+    """Rows between the sequences of a prefill pass that holds a prompt of `seq_len` positions; bucket 0: the exact length (the
+    equal-length entry points pad it to a multiple of 32 themselves)."""
+    return _rup(seq_len, bucket) if bucket else seq_len
+
+
+def prefill_groups(seq_lens: Sequence[int], prefill_group: int, bucket: int = 0) -> List[Tuple[int, int, int]]:
+    """How `caption_batch` cuts its clips into prefill passes: [(first clip, clips, stride)], in order, every clip once; neighbours
+    share a pass while their strides are equal, at most `prefill_group` of them."""
+    out, b, n = [], 0, len(seq_lens)
+    while b < n:
+        st, g = prompt_stride(seq_lens[b], bucket), 1
+        while b + g < n and g < prefill_group and prompt_stride(seq_lens[b + g], bucket) == st:
+            g += 1
+        out.append((b, g, st))
+        b += g
+    return out
+
+
+def check_seq_lens(seq_lens: Sequence[int], stride: int, max_new: int, max_ctx: int) -> List[int]:
+    """The host-side half of the variable-length prefill's contract (the kernels only clamp): 1 <= len <= stride, stride a multiple
+    of 32, len + max_new <= max_ctx."""
+    lens = [int(x) for x in seq_lens]
+    if stride < 32 or stride % 32:
+        raise ValueError(f"stride {stride} is not a positive multiple of 32")
+    for x in lens:
+        if not 1 <= x <= stride:
+            raise ValueError(f"sequence length {x} outside [1, stride {stride}]")
+        if x + max_new > max_ctx:
+            raise ValueError(f"prompt of {x} positions + {max_new} new tokens exceeds max_ctx {max_ctx}")
+    return lens
+
+
+def splice_rows(input_ids: Sequence[int], frames: int, n_kept, strict: bool = False, ntext_cap: Optional[int] = None) -> dict:
+    """The row maps of `AuroraCapEngine.splice_plan` as numpy arrays (no device).  ntext_cap: the text arrays are padded to this many
+    entries with (id 0, row -1); the splice skips entries whose row is negative."""
+    counts = [int(n_kept)] * frames if np.isscalar(n_kept) else [int(c) for c in n_kept]   # per-frame rows (slow-fast: ragged)
+    vis_rows, text_ids, text_rows = [], [], []
+    row, k = 0, 0
+    for tid in input_ids:
+        if tid == IMAGE_TOKEN_INDEX:
+            if k < frames:
+                vis_rows.append(np.arange(row, row + counts[k]))
+                row += counts[k]
+            elif strict:
+                raise IndexError(f"image marker {k} has no frame ({frames} frames)")      # model/utils.py:361
+            k += 1
+        else:
+            text_ids.append(int(tid))
+            text_rows.append(row)
+            row += 1
+    ntext = len(text_ids)
+    if ntext_cap is not None:
+        if ntext > ntext_cap:
+            raise ValueError(f"{ntext} text tokens exceed ntext_cap {ntext_cap}")
+        text_ids += [0] * (ntext_cap - ntext)
+        text_rows += [-1] * (ntext_cap - ntext)
+    vr = np.concatenate(vis_rows) if vis_rows else np.zeros(0, np.int64)
+    return dict(seq_len=row, used=len(vis_rows), n_kept=n_kept, nvis=int(sum(counts[:len(vis_rows)])), ntext=ntext, ntext_cap=ntext_cap,
+                vis_rows=vr.astype(np.int32), text_ids=np.asarray(text_ids, np.int32), text_rows=np.asarray(text_rows, np.int32))
+
+
+def front_end_bucket_key(bank: int, front_cus: int, frames: int, height: int, width: int, r: int, seq: int, plan: dict, bucket: int):
+    """The key under which `caption_stream` keeps a captured front end.  bucket 0: the exact prompt (its length is a kernel argument
+    frozen into the graph).  Otherwise the length is replaced by the stride and the text count by its capacity, both rounded up to
+    the bucket: the lengths and the padded text arrays are static device buffers refilled per clip."""
+    if bucket:
+        return (bank, front_cus, frames, height, width, r, seq, prompt_stride(plan["seq_len"], bucket), plan["used"], plan["nvis"],
+                _rup(max(plan["ntext"], 1), bucket), "var")
+    return (bank, front_cus, frames, height, width, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
+
+
 @dataclass(frozen=True)
 class _BankState:
     """Host view of one generation bank: the batch and max_new of its last accepted begin_batch."""
@@ -59,7 +141,10 @@ class _BankState:
 class AuroraCapEngine:
     def __init__(self, cfg: dict, weights: dict, *, max_frames: int = 8, max_batch: int = 1, max_ctx: int = 4096,
                  max_new_tokens: int = 256, page_tokens: int = 64, use_graph: bool = True, num_banks: int = 1,
-                 max_image: Optional[int] = None, device: str = "cuda:0", spare_slots: int = 0):
+                 max_image: Optional[int] = None, device: str = "cuda:0", spare_slots: int = 0, prompt_bucket: int = 0):
+        # prompt_bucket: 0 = prompts are prefilled at their exact length (equal lengths share a pass, one captured front end per
+        # length); 32 / 64 / 128 = at the next multiple of it, lengths in device memory (`prefill_groups`, `front_end_bucket_key`)
+        self.prompt_bucket = check_prompt_bucket(prompt_bucket)
         if not torch.cuda.is_available():
             raise _lib.AuroraHipError("AuroraCapEngine needs a ROCm GPU (torch.cuda.is_available() is False); "
                                       "there is no CPU fallback")
@@ -357,34 +442,22 @@ class AuroraCapEngine:
             self._pos_cache[key] = tab
         return self._pos_cache[key]
 
-    def splice_plan(self, input_ids: Sequence[int], frames: int, n_kept, strict: bool = False):
+    def splice_plan(self, input_ids: Sequence[int], frames: int, n_kept, strict: bool = False, ntext_cap: Optional[int] = None):
         """Destination-row maps of the prefix splice for one prompt (model/utils.py:198-240 semantics: marker k takes
         frame k; markers beyond the number of frames are dropped), uploaded once.  Re-usable across calls: building it
-        involves blocking host->device copies, which must stay out of a multi-stream pipeline's steady state."""
-        counts = [int(n_kept)] * frames if np.isscalar(n_kept) else [int(c) for c in n_kept]   # per-frame rows (slow-fast: ragged)
-        vis_rows, text_ids, text_rows = [], [], []
-        row, k = 0, 0
-        for tid in input_ids:
-            if tid == IMAGE_TOKEN_INDEX:
-                if k < frames:
-                    vis_rows.append(np.arange(row, row + counts[k]))
-                    row += counts[k]
-                elif strict:
-                    raise IndexError(f"image marker {k} has no frame ({frames} frames)")      # model/utils.py:361
-                k += 1
-            else:
-                text_ids.append(int(tid))
-                text_rows.append(row)
-                row += 1
-        vr = np.concatenate(vis_rows) if vis_rows else np.zeros(0, np.int64)
-        return dict(seq_len=row, used=len(vis_rows), n_kept=n_kept, nvis=int(sum(counts[:len(vis_rows)])), ntext=len(text_ids),
-                    vis_rows=torch.from_numpy(vr.astype(np.int32)).to(self.dev),
-                    text_ids=torch.tensor(text_ids, dtype=torch.int32, device=self.dev),
-                    text_rows=torch.tensor(text_rows, dtype=torch.int32, device=self.dev))
+        involves blocking host->device copies, which must stay out of a multi-stream pipeline's steady state.
+        ntext_cap: pad the text arrays to that many entries (row -1 = unused) for the strided splice (`project_splice(stride=)`)."""
+        p = splice_rows(input_ids, frames, n_kept, strict, ntext_cap)
+        p["len_dev"] = torch.tensor([p["seq_len"]], dtype=torch.int32, device=self.dev)      # what a variable-length prefill reads
+        for k in ("vis_rows", "text_ids", "text_rows"):
+            p[k] = torch.from_numpy(p[k]).to(self.dev)
+        return p
 
     def project_splice(self, vis: torch.Tensor, input_ids: Optional[Sequence[int]] = None, out: Optional[torch.Tensor] = None,
-                       plan: Optional[dict] = None):
-        """vis [frames, n_kept, Dv] + ids (with -200 markers) -> (embeds [L_pad, d] fp16, seq_len)."""
+                       plan: Optional[dict] = None, stride: Optional[int] = None):
+        """vis [frames, n_kept, Dv] + ids (with -200 markers) -> (embeds [L_pad, d] fp16, seq_len).
+        stride: the strided form for a variable-length prefill - embeds holds `stride` rows, every entry of the plan's text arrays
+        is passed (entries with row -1 are skipped on the device, `splice_plan(ntext_cap=)`), no padding row is cleared here."""
         d = self.l["hidden_size"]
         if vis.dim() == 2:                    # flat rows in marker order (frames with different token counts: slow-fast)
             assert plan is not None and plan["nvis"] <= vis.shape[0]
@@ -396,8 +469,17 @@ class AuroraCapEngine:
             assert plan["n_kept"] == vis.shape[1] and plan["used"] <= vis.shape[0]
             seq_len, used = plan["seq_len"], plan["used"]
             vflat = self._h(vis[:used]).reshape(used * plan["n_kept"], -1)
-        embeds = out if out is not None else torch.empty(_rup(seq_len, 32), d, dtype=torch.float16, device=self.dev)
-        assert embeds.shape[0] >= _rup(seq_len, 32) and embeds.is_contiguous()
+        rows = _rup(seq_len, 32) if stride is None else stride
+        embeds = out if out is not None else torch.empty(rows, d, dtype=torch.float16, device=self.dev)
+        assert embeds.shape[0] >= rows and embeds.is_contiguous()
+        if stride is not None:
+            if seq_len > stride:
+                raise ValueError(f"prompt of {seq_len} positions in a stride of {stride}")
+            check(self.ctx, self.L.aur_project_splice_var(self.ctx, vflat.data_ptr(), vflat.shape[0], plan["vis_rows"].data_ptr(),
+                                                          plan["text_ids"].data_ptr(), plan["text_rows"].data_ptr(), plan["text_rows"].numel(),
+                                                          stride, embeds.data_ptr(), self._stream()), "aur_project_splice_var")
+            self._tmp = getattr(self, "_tmp", [])[-64:] + [(vflat, plan)]
+            return embeds, seq_len
         check(self.ctx, self.L.aur_project_splice(self.ctx, vflat.data_ptr(), vflat.shape[0], plan["vis_rows"].data_ptr(),
                                                   plan["text_ids"].data_ptr(), plan["text_rows"].data_ptr(), plan["ntext"], seq_len,
                                                   embeds.data_ptr(), self._stream()), "aur_project_splice")
@@ -425,20 +507,53 @@ class AuroraCapEngine:
     def prefill(self, slot: int, embeds: torch.Tensor, seq_len: int):
         check(self.ctx, self.L.aur_llm_prefill(self.ctx, slot, embeds.data_ptr(), seq_len, self._stream()), "aur_llm_prefill")
 
-    def prefill_batch(self, slot0: int, nseq: int, embeds: torch.Tensor, seq_len: int):
-        """embeds [nseq * round_up(seq_len, 32), d]: equal-length sequences prefetched in ONE pass (large-M GEMMs)."""
+    def _lens_arg(self, seq_lens, nseq: int, stride: int) -> torch.Tensor:
+        """seq_lens of a variable-length prefill as the int32 device tensor the kernels read: a list is checked here (the only place
+        the lengths are known on the host) and uploaded; a device tensor is the caller's promise and is passed through."""
+        if torch.is_tensor(seq_lens):
+            if seq_lens.dtype != torch.int32 or not seq_lens.is_cuda or not seq_lens.is_contiguous() or seq_lens.numel() < nseq:
+                raise ValueError(f"seq_lens must be a contiguous int32 device tensor of at least {nseq} entries")
+            if stride < 32 or stride % 32:
+                raise ValueError(f"stride {stride} is not a positive multiple of 32")
+            return seq_lens
+        lens = check_seq_lens(seq_lens, stride, self._max_new, self.c.max_ctx)
+        if len(lens) != nseq:
+            raise ValueError(f"{len(lens)} lengths for {nseq} sequences")
+        t = torch.tensor(lens, dtype=torch.int32, device=self.dev)
+        self._tmp = getattr(self, "_tmp", [])[-64:] + [t]         # keep alive until consumed
+        return t
+
+    def prefill_batch(self, slot0: int, nseq: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
+        """embeds [nseq * round_up(seq_len, 32), d]: equal-length sequences prefetched in ONE pass (large-M GEMMs).
+        seq_lens (a list, or an int32 device tensor): sequences of DIFFERENT lengths, `seq_len` rows apart (a multiple of 32);
+        every sequence gets bitwise what it gets alone."""
+        if seq_lens is not None:
+            lens = self._lens_arg(seq_lens, nseq, seq_len)
+            check(self.ctx, self.L.aur_llm_prefill_batch_var(self.ctx, slot0, nseq, embeds.data_ptr(), seq_len, lens.data_ptr(), self._stream()),
+                  "aur_llm_prefill_batch_var")
+            return
         check(self.ctx, self.L.aur_llm_prefill_batch(self.ctx, slot0, nseq, embeds.data_ptr(), seq_len, self._stream()),
               "aur_llm_prefill_batch")
 
-    def prefill_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, seq_len: int):
+    def prefill_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
         """The layer stack of `prefill_batch` into KV sequences [seq0, seq0 + nseq) (normally the spare ones,
         `max_batch ..`): touches no decode state, so it may run on another stream while `decode` runs."""
+        if seq_lens is not None:
+            lens = self._lens_arg(seq_lens, nseq, seq_len)
+            check(self.ctx, self.L.aur_llm_prefill_stage_var(self.ctx, seq0, nseq, embeds.data_ptr(), seq_len, lens.data_ptr(), self._stream()),
+                  "aur_llm_prefill_stage_var")
+            return
         check(self.ctx, self.L.aur_llm_prefill_stage(self.ctx, seq0, nseq, embeds.data_ptr(), seq_len, self._stream()),
               "aur_llm_prefill_stage")
 
-    def prefill_commit(self, slot0: int, nseq: int, seq0: int, embeds: torch.Tensor, seq_len: int):
+    def prefill_commit(self, slot0: int, nseq: int, seq0: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
         """On the decode stream, after `prefill_stage` has completed: slots [slot0 ..) take over the pages of sequences
         [seq0 ..) (which get the slots' old pages), are reset, and receive their first tokens."""
+        if seq_lens is not None:
+            lens = self._lens_arg(seq_lens, nseq, seq_len)
+            check(self.ctx, self.L.aur_llm_prefill_commit_var(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), seq_len, lens.data_ptr(),
+                                                              self._stream()), "aur_llm_prefill_commit_var")
+            return
         check(self.ctx, self.L.aur_llm_prefill_commit(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), seq_len, self._stream()),
               "aur_llm_prefill_commit")
 
@@ -490,7 +605,8 @@ class AuroraCapEngine:
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32) -> List[List[int]]:
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
-        Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass.
+        Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
+        `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
         Every kernel on the path is batch-invariant, so each clip gets exactly the ids it gets when captioned alone."""
         B = len(clips)
         if not 1 <= B <= self.max_batch:
@@ -503,18 +619,16 @@ class AuroraCapEngine:
             rs.append(r)
             plans.append(self.splice_plan(ids, px.shape[0], tokens_at_layer(t0, r, self.v["num_hidden_layers"] - 1) - 1))
         self.begin_batch(B, max_new_tokens, eos_id)
-        b = 0
-        while b < B:
-            L, g = plans[b]["seq_len"], 1
-            while b + g < B and g < prefill_group and plans[b + g]["seq_len"] == L:
-                g += 1
+        for b, g, stride in prefill_groups([p["seq_len"] for p in plans], prefill_group, self.prompt_bucket):
+            lens = [plans[b + i]["seq_len"] for i in range(g)]
+            mixed = len(set(lens)) > 1                            # only with a bucket: lengths go to the device, rows beyond them are don't-care
+            L = stride if mixed else lens[0]
             Lp = _rup(L, 32)
             buf = torch.empty(g * Lp, d, dtype=torch.float16, device=self.dev)
             for i in range(g):
                 vis = self.vit_encode(clips[b + i][0], rs[b + i])
                 self.project_splice(vis, out=buf[i * Lp:(i + 1) * Lp], plan=plans[b + i])
-            self.prefill_batch(b, g, buf, L)
-            b += g
+            self.prefill_batch(b, g, buf, L, seq_lens=lens if mixed else None)
         done = 1
         while done < max_new_tokens:
             n = min(check_every, max_new_tokens - done) if eos_id is not None else max_new_tokens - done
@@ -622,7 +736,8 @@ class AuroraCapEngine:
         current stream.  Graphs are captured per bank (its page table is baked in), per `front_cus` (so is the persistent GEMM's grid)
         and per shape bucket - (frames, H, W, r, prompt structure, seq) - on first use and kept (at most `front_graph_cap`, least
         recently used evicted): the per-bucket capture of the reference tree's serving engine
-        (src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279).  Returns (embeds, seq_len) for `prefill_commit`;
+        (src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279).  Returns (embeds, seq_len) for `prefill_commit`
+        - with `prompt_bucket`, (embeds, (stride, lengths buffer)): the bucket no longer depends on the exact prompt length -;
         `embeds` is the bucket's static buffer: the caller orders the next replay of the same bucket (same `seq`) after that commit."""
         if px.dim() != 4 or px.shape[1] != self.v.get("num_channels", 3):
             raise ValueError(f"pixel_values must be [frames, {self.v.get('num_channels', 3)}, H, W], got {tuple(px.shape)}")
@@ -634,7 +749,12 @@ class AuroraCapEngine:
         plan = self.splice_plan(ids, F, n_kept)
         if plan["seq_len"] < 1 or plan["seq_len"] + self._max_new > self.c.max_ctx:
             raise ValueError(f"prompt of {plan['seq_len']} positions + {self._max_new} new tokens exceeds max_ctx {self.c.max_ctx}")
-        key = (self._bank, front_cus, F, H, W, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
+        pb = self.prompt_bucket
+        key = front_end_bucket_key(self._bank, front_cus, F, H, W, r, seq, plan, pb)
+        if pb:
+            stride, ntext_cap = key[7], key[10]
+            if stride > _rup(self.c.max_ctx, self.c.page_tokens):
+                raise ValueError(f"stride {stride} of prompt bucket {pb} exceeds the KV pages of a sequence (max_ctx {self.c.max_ctx})")
         cache = self._front_graphs
         fg = cache.pop(key, None)
         if fg is None:
@@ -644,14 +764,17 @@ class AuroraCapEngine:
                 if old._last is not None:
                     old._last.synchronize()
                 old.close()
-            fg = FrontEndGraph(self, 1, F, H, W, r, plan, seq0=seq)
+            if pb:
+                fg = FrontEndGraph(self, 1, F, H, W, r, self.splice_plan(ids, F, n_kept, ntext_cap=ntext_cap), seq0=seq, stride=stride)
+            else:
+                fg = FrontEndGraph(self, 1, F, H, W, r, plan, seq0=seq)
             fg._last = None
         cache[key] = fg                                           # most recently used last
         fg.load(self._h(px), [plan])
         fg.launch()
         fg._last = torch.cuda.Event()
         fg._last.record(torch.cuda.current_stream(self.dev))
-        return fg.embeds, plan["seq_len"]
+        return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"])
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True):
         from collections import deque
@@ -677,7 +800,10 @@ class AuroraCapEngine:
                         idx, seq, emb, L, ev = staged.popleft()
                         sD.wait_event(ev)
                         emb.record_stream(sD)
-                        self.prefill_commit(s, 1, seq, emb, L)
+                        if isinstance(L, tuple):                  # a bucketed front end: (stride, the graph's static lengths buffer)
+                            self.prefill_commit(s, 1, seq, emb, L[0], seq_lens=L[1])
+                        else:
+                            self.prefill_commit(s, 1, seq, emb, L)
                         evc = torch.cuda.Event()
                         evc.record(sD)
                         reusable[seq] = evc
@@ -901,12 +1027,18 @@ class FrontEndGraph:
     """
 
     def __init__(self, eng: "AuroraCapEngine", group: int, frames: int, height: int, width: int, r: int, plan: dict, seq0: int,
-                 embeds: Optional[torch.Tensor] = None, prefill: str = "stage", slot0: int = 0):
+                 embeds: Optional[torch.Tensor] = None, prefill: str = "stage", slot0: int = 0, stride: Optional[int] = None):
         v, d = eng.v, eng.l["hidden_size"]
+        # stride: the variable-length form.  The sequences lie `stride` rows apart, `plan` is a padded one (`splice_plan(ntext_cap=)`,
+        # its capacity becomes the bucket's) and the lengths are one more static buffer, `lens`, read by the captured kernels at replay:
+        # the graph serves every prompt of this structure whose length fits the stride and whose text fits the capacity.
+        self.stride = stride
         self.eng, self.group, self.frames, self.r, self.seq0 = eng, group, frames, r, seq0
         self.bank = eng._bank                                     # the graph writes through this bank's page table
         self.seq_len = plan["seq_len"]
-        self.mseq = _rup(self.seq_len, 32)
+        self.mseq = _rup(self.seq_len, 32) if stride is None else stride
+        if stride is not None and (plan.get("ntext_cap") is None or self.seq_len > stride):
+            raise ValueError("the variable-length front end needs a padded splice plan that fits the stride")
         t0 = (height // v["patch_size"]) * (width // v["patch_size"]) + 1
         self.n_kept = tokens_at_layer(t0, r, v["num_hidden_layers"] - 1) - 1
         assert not np.isscalar(plan["n_kept"]) or plan["n_kept"] == self.n_kept
@@ -916,7 +1048,8 @@ class FrontEndGraph:
         self.embeds = embeds if embeds is not None else torch.zeros(group * self.mseq, d, dtype=torch.float16, device=dev)
         assert self.embeds.shape[0] >= group * self.mseq and self.embeds.is_contiguous()
         # the bucket's splice plans: same structure as `plan` (row maps of one prompt), contents replaced per clip by load()
-        self.used, self.nvis, self.ntext = plan["used"], plan["nvis"], plan["ntext"]
+        self.used, self.nvis, self.ntext = plan["used"], plan["nvis"], plan["ntext"] if stride is None else plan["ntext_cap"]
+        self.lens = torch.ones(group, dtype=torch.int32, device=dev)
         self.vis_rows = torch.zeros(group, max(self.nvis, 1), dtype=torch.int32, device=dev)
         self.text_ids = torch.zeros(group, max(self.ntext, 1), dtype=torch.int32, device=dev)
         self.text_rows = torch.zeros(group, max(self.ntext, 1), dtype=torch.int32, device=dev)
@@ -927,15 +1060,18 @@ class FrontEndGraph:
             self.vis_rows[j].copy_(plan["vis_rows"])
             self.text_ids[j].copy_(plan["text_ids"])
             self.text_rows[j].copy_(plan["text_rows"])
+            self.lens[j:j + 1].copy_(plan["len_dev"])
 
         def run():
             eng.vit_encode(self.pixels, r, out=self.vis)
             for j in range(group):
-                eng.project_splice(self.vis[j * frames:(j + 1) * frames], plan=self._plans[j], out=self.embeds[j * self.mseq:(j + 1) * self.mseq])
+                eng.project_splice(self.vis[j * frames:(j + 1) * frames], plan=self._plans[j], out=self.embeds[j * self.mseq:(j + 1) * self.mseq],
+                                   stride=stride)
+            var = dict(seq_lens=self.lens) if stride is not None else {}
             if prefill == "stage":
-                eng.prefill_stage(seq0, group, self.embeds, self.seq_len)
+                eng.prefill_stage(seq0, group, self.embeds, self.mseq if var else self.seq_len, **var)
             elif prefill == "batch":
-                eng.prefill_batch(slot0, group, self.embeds, self.seq_len)
+                eng.prefill_batch(slot0, group, self.embeds, self.mseq if var else self.seq_len, **var)
             else:
                 assert prefill == "none"
 
@@ -949,6 +1085,16 @@ class FrontEndGraph:
         if plans is not None:
             assert len(plans) == self.group
             for j, pl in enumerate(plans):
+                if self.stride is not None:
+                    if (pl["used"], pl["nvis"]) != (self.used, self.nvis) or pl["seq_len"] > self.stride or pl["ntext"] > self.ntext:
+                        raise ValueError("splice plan of another shape bucket")
+                    n = pl["ntext"]                               # the clip's own plan may be exact or padded: entries beyond n are unused
+                    self.text_rows[j].fill_(-1)
+                    self.vis_rows[j, :self.nvis].copy_(pl["vis_rows"], non_blocking=True)
+                    self.text_ids[j, :n].copy_(pl["text_ids"][:n], non_blocking=True)
+                    self.text_rows[j, :n].copy_(pl["text_rows"][:n], non_blocking=True)
+                    self.lens[j:j + 1].copy_(pl["len_dev"], non_blocking=True)
+                    continue
                 if (pl["seq_len"], pl["used"], pl["nvis"], pl["ntext"]) != (self.seq_len, self.used, self.nvis, self.ntext):
                     raise ValueError("splice plan of another shape bucket")
                 self.vis_rows[j, :self.nvis].copy_(pl["vis_rows"], non_blocking=True)

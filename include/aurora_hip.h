@@ -130,6 +130,13 @@ int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t 
 int aur_project_splice(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows,
                        const int32_t* text_ids, const int32_t* text_rows, int32_t ntext,
                        int32_t seq_len, void* embeds, void* stream);
+/* The same for one sequence of a variable-length prefill: text_ids / text_rows hold ntext_cap entries of which those with
+ * text_rows[j] < 0 are unused and skipped (a prompt shorter than the capacity pads with -1), so the call needs no length and a captured
+ * graph serves every prompt that fits the capacity.  embeds: the sequence's `stride` rows (stride as in aur_llm_prefill_batch_var);
+ * rows that no entry names are left as they are - the variable-length prefill clears [len, stride) itself.  Same STREAM RULE. */
+int aur_project_splice_var(aur_ctx* ctx, const void* vis, int32_t nvis, const int32_t* vis_rows,
+                           const int32_t* text_ids, const int32_t* text_rows, int32_t ntext_cap,
+                           int32_t stride, void* embeds, void* stream);
 
 /* Greedy generation state: replaces llm.generate(inputs_embeds=..., do_sample=False, max_new_tokens=N)
  * (inference.py:89-96).  eos_id < 0 disables the EOS stop (benchmark: fixed-length outputs). */
@@ -158,6 +165,22 @@ int aur_llm_prefill_batch(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embed
  *           produces their first tokens from the last prompt rows of `embeds`.  seq0 == slot0: no exchange. */
 int aur_llm_prefill_stage(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t seq_len, void* stream);
 int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream);
+/* Variable-length forms of the three calls above: prompts of DIFFERENT lengths in one pass, the lengths in device memory.
+ * embeds is fp16 [nseq * stride, llm_hidden], stride a multiple of 32 and at most the positions of a sequence's KV pages
+ * (ceil(max_ctx / page_tokens) * page_tokens); sequence i occupies rows [i * stride, i * stride + len_i), len_i = seq_lens_dev[i]:
+ * int32 in DEVICE memory, caller-owned, read by the kernels when the work runs - it must stay valid (and unchanged) until then.  The
+ * host never reads the lengths: no synchronisation, no allocation, the calls are enqueue-only and may be recorded with aur_graph_begin.
+ * A capture freezes stride, nseq, the slot / sequence ids and the pointers - NOT the lengths: refill the lengths buffer (and embeds)
+ * before each replay.  Because the host cannot check them, every kernel clamps len_i into [1, stride]; that len_i + max_new_tokens <=
+ * max_ctx is the CALLER'S promise (aurora_amd.engine checks it where the lengths are known).
+ * Rows [len_i, stride) of embeds are don't-care on input - stale states of an earlier, longer prompt, Inf / NaN patterns -: the prefill
+ * clears them itself before the first layer, they stay zero in every layer, and the K / V written for positions [len_i, stride) are
+ * zeros until decode steps overwrite them.  For sequence i the first token, the logits row, every K / V value at positions < len_i and
+ * the decode position are BITWISE those of aur_llm_prefill(slot, embeds_i, len_i).  aur_llm_prefill_commit_var reads only row
+ * len_i - 1 of each sequence and takes the same (stride, seq_lens_dev) its stage was given. */
+int aur_llm_prefill_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
+int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
+int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
 /* Run `steps` decode steps for slots [0, batch): one new token per unfinished slot per step. */
 int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream);
 /* Synchronises the stream and copies results to host: ids [batch * max_new_tokens], lens [batch]. */
@@ -180,7 +203,7 @@ int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_d
 /* ---- captured front ends (the reference tree's serving engine captures one graph per shape bucket and copies the inputs into the
  * graph's static buffers before every replay: src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279) ------------
  * aur_graph_begin opens a hipGraph capture on `stream` (thread-local mode); every enqueue-only call of this ctx that follows on that
- * stream from the same thread - aur_vit_encode(_hw), aur_project_splice, aur_llm_prefill / _batch / _stage / _commit, aur_slot_reset /
+ * stream from the same thread - aur_vit_encode(_hw), aur_project_splice(_var), aur_llm_prefill / _batch / _stage / _commit (and their _var forms), aur_slot_reset /
  * _retire / _collect, the kernel-level entry points - is recorded instead of run; aur_graph_end instantiates the recording and returns
  * a handle (>= 1) that aur_graph_launch replays with one call.  Pointers, shapes, KV sequence ids, the ctx's gemm_* knobs and the
  * current bank (whose page table the prefill writes through) are frozen at capture time: a serving loop keeps one graph per (bank,
