@@ -36,6 +36,11 @@ class AurConfig(C.Structure):
     ]
 
 
+class AurSampling(C.Structure):
+    """aur_sampling: one slot's sampling parameters (aurora_amd.sampling.RECORD is the numpy form of the same layout)"""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("stream", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class AuroraHipError(RuntimeError):
     pass
 
@@ -92,6 +97,8 @@ SIGNATURES = {
     "aur_layernorm": (C.c_int, [_P, _P, _I, _I, _P, _P, C.c_float, _P, _P]),
     "aur_rmsnorm": (C.c_int, [_P, _P, _I, _I, _P, C.c_float, _P, _P]),
     "aur_vit_layer": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aur_slot_sampling": (C.c_int, [_P, _I, _I, _P, _P]),
+    "aur_sample_rows": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "aur_copy_logits": (C.c_int, [_P, _P, _P]),
     "aur_set_option": (C.c_int, [_P, C.c_char_p, _L]),
     "aur_microbench": (C.c_int, [_P, C.c_char_p, _I, C.POINTER(C.c_double), _P]),

@@ -28,11 +28,7 @@
 //   and V^T fragments (rows = d) stream from the paged cache as contiguous 1 KiB pieces; dot products on the VALU (v_dot2c_f32_f16),
 //   one query per (sequence, head): see decode_attn_dot_kernel.
 #include "kernels.h"
-
-// address (halves) of the 16-byte piece holding x[b][k .. k+8) (k % 8 == 0) in x-fragment form
-__device__ __forceinline__ int64_t xfrag_piece(int b, int k, int K32) {
-    return ((((int64_t)(b >> 4) * K32 + (k >> 5)) * 64) + ((k >> 3) & 3) * 16 + (b & 15)) * 8;
-}
+#include "advance.h"      // xfrag_piece, SSQ_SCALE, ssq_set, and the token pick's shared halves
 
 // Lane whose 16-byte piece of an x fragment this lane loads for column group nb.  A lane whose batch row lies outside the live range
 // [b_lo, b_hi) reads the piece of a LIVE row of its group instead of its own: the same address as that lane, so the wave's request
@@ -49,7 +45,6 @@ __device__ __forceinline__ int xsrc_lane(const SkinnyArgs& a, int lane, int nb) 
     return (lane & ~15) | cc;
 }
 
-#define SSQ_SCALE 268435456.0f      /* 2^28 */
 // sum(x^2) accumulators are striped over AUR_SSQ_SLOTS copies, [slot][AUR_MAX_BATCH]: the residual-producing epilogues add into
 // slot (n16 tile % SLOTS), so the 256 integer atomics that hit one row's accumulator per projection spread over 16 L2 lines
 // instead of queueing on one (they cost the o / down projections ~5 us each at 64 rows: 18.4 us in the engine vs 13.7 us with a
@@ -59,11 +54,6 @@ __device__ __forceinline__ float ssq_to_rstd(const unsigned long long* ssq, int 
 #pragma unroll
     for (int sl = 0; sl < AUR_SSQ_SLOTS; ++sl) s += ssq[sl * AUR_MAX_BATCH + b];
     return rsqrtf((float)((double)s * (1.0 / 268435456.0)) / (float)k + eps);
-}
-__device__ __forceinline__ void ssq_set(unsigned long long* ssq, int b, unsigned long long v) {        // one writer per row
-    ssq[b] = v;
-#pragma unroll
-    for (int sl = 1; sl < AUR_SSQ_SLOTS; ++sl) ssq[sl * AUR_MAX_BATCH + b] = 0ull;
 }
 __device__ __forceinline__ void ssq_clear(unsigned long long* ssq, int tid) {                          // tid < AUR_MAX_BATCH
 #pragma unroll
@@ -1255,13 +1245,6 @@ hipError_t launch_decode_attention(const DecAttnArgs& a, hipStream_t s) {
 // 1024 threads scan the row with 16-byte loads (one 256-thread block took 125 dependent 4-byte loads per thread: 40 us per step whatever
 // the batch - 1 % of an 8-slot step); the FIRST maximum wins whatever the scan order (value, then index).  The embedding copy and its
 // sum(x^2) keep the 256-thread loop and tree of rounds 1-3: same additions in the same order, same bits.
-#define ARGMAX_THREADS 1024
-__device__ __forceinline__ void argmax_take(float& best, int& bi, float v, int i) {
-    if (v > best || (v == best && i < bi)) {
-        best = v;
-        bi = i;
-    }
-}
 __global__ __launch_bounds__(ARGMAX_THREADS) void argmax_advance_kernel(const float* __restrict__ logits, int b0, int vocab,
                                                              const half_t* __restrict__ embed, int d, int eos_id, int max_new,
                                                              int32_t* __restrict__ out_ids, int32_t* __restrict__ out_len,
@@ -1271,68 +1254,11 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void argmax_advance_kernel(const fl
                                                              int len_cap) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    const int b = b0 + blockIdx.x, tid = threadIdx.x;
-    const float* lg = logits + (int64_t)b * vocab;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if ((vocab & 3) == 0) {                        // rows stay 16-byte aligned
-        const int n4 = vocab >> 2;
-#pragma unroll 4
-        for (int i = tid; i < n4; i += ARGMAX_THREADS) {
-            const f4 v = *(const f4*)(lg + 4 * i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) argmax_take(best, bi, v[j], 4 * i + j);
-        }
-    } else {
-        for (int i = tid; i < vocab; i += ARGMAX_THREADS) argmax_take(best, bi, lg[i], i);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) argmax_take(best, bi, __shfl_xor(best, o), __shfl_xor(bi, o));
-    if ((tid & 63) == 0) {
-        sv[tid >> 6] = best;
-        si[tid >> 6] = bi;
-    }
+    const int b = b0 + blockIdx.x;
+    const int tok = row_first_argmax(logits + (int64_t)b * vocab, vocab, sv, si);      // advance.h
     __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < ARGMAX_THREADS / 64; ++w) argmax_take(best, bi, sv[w], si[w]);
-        si[0] = bi;
-    }
-    __syncthreads();
-    int tok = si[0];
-    if (tok == 0x7fffffff) tok = 0;
-    __syncthreads();
-    if (tid == 0) {
-        const bool was_finished = finished[b] != 0;
-        if (!was_finished) {
-            const int n = out_len[b];
-            if (n < max_new) {
-                out_ids[(int64_t)b * max_new + n] = tok;
-                out_len[b] = n + 1;
-            }
-            if (tok == eos_id || n + 1 >= max_new) finished[b] = 1;     // EOS, or the output row is full
-        }
-        if (set_pos_lens) pos[b] = var_len(set_pos_lens, blockIdx.x, len_cap);       // a variable-length prefill: each slot's own length
-        else if (set_pos >= 0) pos[b] = set_pos;
-        // a finished (or idle) slot stops advancing: it keeps recomputing one position inside its own pages, so extra
-        // decode steps (other slots still running, continuous batching) can never walk it past its KV allocation
-        if (advance_pos && !was_finished) pos[b] += 1;
-    }
-    float ss = 0.f;
-    if (tid < 256) {
-        for (int cidx = tid; cidx < (d >> 3); cidx += 256) {
-            const h8 v = *(const h8*)(embed + (int64_t)tok * d + cidx * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += (float)v[j] * (float)v[j];
-            *(h8*)(xf + xfrag_piece(b, cidx * 8, d >> 5)) = v;
-        }
-        sv[tid] = ss;
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {            // fixed-order tree: deterministic
-        if (tid < o) sv[tid] += sv[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) ssq_set(ssq, b, (unsigned long long)__float2ll_rn(sv[0] * SSQ_SCALE));
+    advance_tail(b, blockIdx.x, tok, embed, d, eos_id, max_new, out_ids, out_len, finished, pos, xf, ssq, advance_pos, set_pos, set_pos_lens,
+                 len_cap, sv);
 }
 
 hipError_t launch_argmax_advance(const float* logits, int b0, int nb, int vocab, const half_t* embed, int d, int eos_id,

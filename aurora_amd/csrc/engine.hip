@@ -83,6 +83,7 @@ struct aur_ctx {
     int* d_row_cnt = nullptr;                                                   // its arrival counters (zero between launches)
     int attn_local = 1;                                                         // 1: workgroup-local join of the decode attention's splits where it applies (mk_dec_attn); 0 = always decode_attn_combine_kernel (A/B and test)
     int tome_fused_ln = 1;                                                      // 1: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge launch (bitwise norm_kernel's result; 0 = its own launch, A/B and test only)
+    int sampling = 0, sample_stage = 1;                                         // the token pick: 0 argmax_advance_kernel, 1 sample_advance_kernel (row staged in LDS / re-read from L2)
     int fused_reduce = 0;                                                       // 1: the split-K reduce runs inside the projection kernel
     // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graphs) so
     // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  Every generation call
@@ -92,6 +93,7 @@ struct aur_ctx {
         unsigned long long *s_ssq_mlp, *s_ssq_attn;
         float* d_logits;
         int32_t *s_pos, *s_ids, *s_len, *s_fin;
+        aur_sampling* s_samp;                                // per-slot sampling parameters (aur_slot_sampling); temperature 0 = greedy
         int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
         int batch = 0, max_new = 0, eos = -1;
         hipGraphExec_t graph = nullptr, graph_h = nullptr;   // decode step: full grid / half grid (decode_half)
@@ -287,6 +289,7 @@ static int64_t carve(aur_ctx* c, char* base) {
         K.s_ids = k.take<int32_t>(B * g.max_new_tokens);
         K.s_len = k.take<int32_t>(B);
         K.s_fin = k.take<int32_t>(B);
+        K.s_samp = k.take<aur_sampling>(B);
     }
     c->d_q = k.take<half_t>(B * d);
     c->d_attn = k.take<half_t>(Bp * d);                    // attention output  (x-fragment form)
@@ -324,7 +327,7 @@ extern "C" int aur_create(const aur_config* cfg, aur_ctx** out) {
     {
         hipError_t e;
         if ((e = gemm_init()) != hipSuccess || (e = attn_init()) != hipSuccess || (e = tome_init()) != hipSuccess ||
-            (e = skinny_init()) != hipSuccess || (e = gemm256_init()) != hipSuccess)
+            (e = skinny_init()) != hipSuccess || (e = gemm256_init()) != hipSuccess || (e = sample_init()) != hipSuccess)
             return aur_fail(nullptr, AUR_ERR_HIP, "kernel attribute init failed (is a gfx950 GPU visible?): %s", hipGetErrorString(e));
     }
     if (g.proj_depth < 0 || g.proj_depth > 8) return aur_fail(nullptr, AUR_ERR_ARG, "proj_depth must be 0 (= 2) or 1 .. 8");
@@ -950,6 +953,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.s_len, 0, (size_t)g.max_batch * 4, s));
     CK(hipMemsetAsync(K.s_fin, 0, (size_t)g.max_batch * 4, s));
     CK(hipMemsetAsync(K.s_pos, 0, (size_t)g.max_batch * 4, s));
+    CK(hipMemsetAsync(K.s_samp, 0, (size_t)g.max_batch * sizeof(aur_sampling), s));      // every slot greedy until aur_slot_sampling says otherwise
     CK(hipMemsetAsync(K.s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
     const size_t bp = (size_t)rup(g.max_batch, 16);       // unused fragment lanes must hold finite values
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
@@ -969,8 +973,12 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     h.mode = SK_LOGITS; h.out32 = K.d_logits; h.b_lo = b0; h.b_hi = b0 + nb; h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
     h.variant = ctx->skinny_variant;
     CK(launch_skinny(h, s));
-    CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
-                             K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
+    if (ctx->sampling)
+        CK(launch_sample_advance(K.d_logits, b0, nb, g.llm_vocab, K.s_samp, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
+                                 K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap, ctx->sample_stage));
+    else
+        CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
+                                 K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
     return AUR_OK;
 }
 
@@ -1506,6 +1514,21 @@ extern "C" int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int
     CK(hipMemcpyAsync(lens_dev, K.s_len + slot0, (size_t)nslots * 4, hipMemcpyDeviceToDevice, s));
     return AUR_OK;
 }
+extern "C" int aur_slot_sampling(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_sampling* params_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_sampling")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (nslots < 1 || slot0 + nslots > K.batch || !params_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_sampling: slots [%d, %d) outside the batch of %d, or null parameters", slot0, slot0 + nslots, K.batch);
+    CK(hipMemcpyAsync(K.s_samp + slot0, params_dev, (size_t)nslots * sizeof(aur_sampling), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AUR_OK;
+}
+extern "C" int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const aur_sampling* params_dev,
+                               const int32_t* n_dev, int32_t* tokens_out, int32_t* kept_out, void* stream) {
+    if (!ctx || !logits || !params_dev || !n_dev || !tokens_out) return aur_fail(ctx, AUR_ERR_ARG, "aur_sample_rows: null argument");
+    if (rows < 1 || rows > 65535 || vocab < 1) return aur_fail(ctx, AUR_ERR_ARG, "aur_sample_rows: rows %d outside [1, 65535] or vocab %d < 1", rows, vocab);
+    if ((uintptr_t)logits & 15) return aur_fail(ctx, AUR_ERR_ARG, "aur_sample_rows: logits must be 16-byte aligned");
+    CK(launch_sample_rows(logits, rows, vocab, params_dev, n_dev, tokens_out, kept_out, (hipStream_t)stream, ctx->sample_stage));
+    return AUR_OK;
+}
 extern "C" int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream) {
     const aur_ctx::Bank& K = ctx->bank();
     if (K.batch < 1 || !dst_dev) return aur_fail(ctx, AUR_ERR_STATE, "aur_copy_logits: no active batch");
@@ -1551,6 +1574,10 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
         // -1 (default): none.  The step's graphs are re-captured.
         if (value < -1 || value >= ctx->cfg.llm_layers) return aur_fail(ctx, AUR_ERR_ARG, "decode_stamp_layer must be -1 or a layer index");
         ctx->stamp_layer = (int)value;
+    } else if (!strcmp(name, "sampling") || !strcmp(name, "sample_stage")) {
+        // which kernel picks the token (and how it reads its row) is frozen inside the captured decode graphs: they are re-captured
+        if (value < 0 || value > 1) return aur_fail(ctx, AUR_ERR_ARG, "%s must be 0 or 1", name);
+        (!strcmp(name, "sampling") ? ctx->sampling : ctx->sample_stage) = (int)value;
     } else if (!strcmp(name, "decode_half_grid")) {
         // the following aur_llm_decode calls go to a stream that owns half of the CUs: QKV / gate-up launch half as many workgroups
         // with twice the tiles (decode.hip launch_skx_nb); bitwise the same tokens.  Keeps both captured graphs.
@@ -1591,6 +1618,13 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
             h.xf = K.d_x; h.W = ctx->l_head_w; h.B = K.batch; h.b_lo = 0; h.b_hi = K.batch; h.Npad = ctx->l_vocab_pad; h.K = d;
             h.n_real = g.llm_vocab; h.mode = SK_LOGITS; h.out32 = K.d_logits; h.variant = ctx->skinny_variant;
             CK(launch_skinny(h, s));
+        } else if (!strcmp(kernel, "dec_pick")) {              // the token pick alone, on the logits of the last step: whichever kernel the "sampling" mode selects
+            if (ctx->sampling)
+                CK(launch_sample_advance(K.d_logits, 0, K.batch, g.llm_vocab, K.s_samp, ctx->l_embed, d, K.eos, K.max_new, K.s_ids, K.s_len, K.s_fin,
+                                         K.s_pos, K.d_x, K.s_ssq_mlp, 1, -1, s, nullptr, 0, ctx->sample_stage));
+            else
+                CK(launch_argmax_advance(K.d_logits, 0, K.batch, g.llm_vocab, ctx->l_embed, d, K.eos, K.max_new, K.s_ids, K.s_len, K.s_fin, K.s_pos,
+                                         K.d_x, K.s_ssq_mlp, 1, -1, s));
         } else {
             int bit = !strcmp(kernel, "pre_norm") ? 1 : !strcmp(kernel, "pre_qkv") ? 2 : !strcmp(kernel, "pre_attn") ? 4 : !strcmp(kernel, "pre_o") ? 8
                       : !strcmp(kernel, "pre_gateup") ? 32 : !strcmp(kernel, "pre_down") ? 64 : 0;

@@ -201,3 +201,14 @@ hipError_t launch_argmax_advance(const float* logits, int b0, int nb, int vocab,
                                  int max_new, int32_t* out_ids, int32_t* out_len, int32_t* finished, int32_t* pos,
                                  half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s,
                                  const int32_t* set_pos_lens = nullptr, int len_cap = 0);      // non-null: pos[b0 + i] = var_len(set_pos_lens, i, len_cap)
+
+// ---- sample.hip: the sampled pick (temperature / top-k / top-p, counter-based draw); per-slot parameters in device memory
+struct aur_sampling;
+hipError_t sample_init();
+// stage: 1 = the row is staged in LDS when it fits, 0 = re-read from global memory on every pass (same token either way)
+hipError_t launch_sample_advance(const float* logits, int b0, int nb, int vocab, const aur_sampling* params, const half_t* embed, int d,
+                                 int eos_id, int max_new, int32_t* out_ids, int32_t* out_len, int32_t* finished, int32_t* pos, half_t* xf,
+                                 unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s, const int32_t* set_pos_lens,
+                                 int len_cap, int stage);
+hipError_t launch_sample_rows(const float* logits, int rows, int vocab, const aur_sampling* params, const int32_t* n_dev,
+                              int32_t* tokens_out, int32_t* kept_out, hipStream_t s, int stage);

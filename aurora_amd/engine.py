@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import sampling as S
 from ._lib import AurConfig, check
 
 IMAGE_TOKEN_INDEX = -200     # src/xtuner/xtuner/utils/constants.py:4
@@ -197,6 +198,8 @@ class AuroraCapEngine:
         self.front_graph_cap = 16
         self._banks = [_BankState(), _BankState()]       # the C side's current bank is self._bank
         self._bank = 0
+        self._sampling_mode = False                      # ctx option "sampling": flipped by the first sampling request, sticky
+        self._samp_stage = None                          # device staging of aur_sampling records, one row per (bank, slot)
         self.c = c
         self.v, self.l = v, l
         self.max_new_tokens = max_new_tokens
@@ -579,10 +582,64 @@ class AuroraCapEngine:
         torch.cuda.synchronize()
         return out
 
-    def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32):
-        """Greedy generation for a batch of already-spliced prefixes (one KV slot per sequence)."""
+    # ------------------------------------------------------------------ sampling
+    def _sampling_on(self):
+        """The first sampling request switches the ctx's token pick to sample_advance_kernel (decode graphs are re-captured once);
+        slots whose temperature is 0 keep the greedy rule bit for bit.  A process that never samples never gets here."""
+        if not self._sampling_mode:
+            self.set_option("sampling", 1)
+            self._sampling_mode = True
+
+    def slot_sampling(self, slot0: int, recs: np.ndarray):
+        """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_sampling records (`sampling.records`): staged in
+        device memory and copied into the bank when the stream gets there - before the prefill / commit that picks the first token."""
+        recs = np.ascontiguousarray(recs, dtype=S.RECORD)
+        n = len(recs)
+        if n < 1 or slot0 < 0 or slot0 + n > self.max_batch:
+            raise ValueError(f"slots [{slot0}, {slot0 + n}) outside an engine of {self.max_batch} slots")
+        if self._samp_stage is None:
+            self._samp_stage = torch.zeros(2 * self.max_batch, S.RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        row0 = self._bank * self.max_batch + slot0
+        dst = self._samp_stage[row0: row0 + n]
+        dst.copy_(torch.from_numpy(recs.view(np.uint8).reshape(n, S.RECORD.itemsize).copy()))      # torch's current stream: _stream() orders ours behind it
+        check(self.ctx, self.L.aur_slot_sampling(self.ctx, slot0, n, dst.data_ptr(), self._stream()), "aur_slot_sampling")
+
+    def _begin_sampled(self, samp: Optional[dict], streams, B: int):
+        """After begin_batch (which makes every slot greedy): the records of slots [0, B) for a sampling call."""
+        if samp is None:
+            return
+        streams = list(range(B)) if streams is None else [int(x) for x in streams]
+        if len(streams) != B:
+            raise ValueError(f"{len(streams)} streams for {B} sequences")
+        self.slot_sampling(0, S.records(samp, streams))
+
+    def sample_rows(self, logits: torch.Tensor, recs: np.ndarray, n: Sequence[int]):
+        """The sampled pick alone (aur_sample_rows): logits fp32 [rows, vocab] on the device, one aur_sampling record and one token
+        index per row -> (tokens, kept-set sizes) as numpy int32."""
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.is_contiguous() and logits.dim() == 2
+        rows, vocab = logits.shape
+        recs = np.ascontiguousarray(recs, dtype=S.RECORD)
+        assert len(recs) == rows and len(n) == rows
+        prm = torch.from_numpy(recs.view(np.uint8).reshape(rows, S.RECORD.itemsize).copy()).to(self.dev)
+        nd = torch.tensor([int(x) for x in n], dtype=torch.int32, device=self.dev)
+        tok = torch.empty(rows, dtype=torch.int32, device=self.dev)
+        kept = torch.empty(rows, dtype=torch.int32, device=self.dev)
+        check(self.ctx, self.L.aur_sample_rows(self.ctx, logits.data_ptr(), rows, vocab, prm.data_ptr(), nd.data_ptr(), tok.data_ptr(),
+                                               kept.data_ptr(), self._stream()), "aur_sample_rows")
+        torch.cuda.synchronize()
+        return tok.cpu().numpy(), kept.cpu().numpy()
+
+    def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
+                 sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None):
+        """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
+        sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
+        the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours."""
         B = len(embeds_list)
+        samp = S.check_sampling(sampling)
+        if samp is not None:
+            self._sampling_on()
         self.begin_batch(B, max_new_tokens, eos_id)
+        self._begin_sampled(samp, streams, B)
         for b in range(B):
             self.prefill(b, embeds_list[b], seq_lens[b])
         done = 1
@@ -595,20 +652,23 @@ class AuroraCapEngine:
         return self.outputs()
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
-                    eos_id: Optional[int] = 2) -> List[int]:
-        """Whole path for one clip: the call sequence of inference.py:87-96."""
+                    eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0) -> List[int]:
+        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream: as in `generate`."""
         r = self.tome_r(token_kept_ratio, pixels.shape[-2], pixels.shape[-1])
         vis = self.vit_encode(pixels, r)
         emb, L = self.project_splice(vis, input_ids)
-        return self.generate([emb], [L], max_new_tokens, eos_id)[0]
+        return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream])[0]
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
-                      eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32) -> List[List[int]]:
+                      eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
+                      streams: Optional[Sequence[int]] = None) -> List[List[int]]:
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
-        Every kernel on the path is batch-invariant, so each clip gets exactly the ids it gets when captioned alone."""
+        Every kernel on the path is batch-invariant, so each clip gets exactly the ids it gets when captioned alone.
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip i draws with stream streams[i] (default: i)."""
         B = len(clips)
+        samp = S.check_sampling(sampling)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{B} clips for an engine built with max_batch={self.max_batch}")
         d = self.l["hidden_size"]
@@ -618,7 +678,10 @@ class AuroraCapEngine:
             t0 = (px.shape[-2] // self.v["patch_size"]) * (px.shape[-1] // self.v["patch_size"]) + 1     # as vit_encode counts them
             rs.append(r)
             plans.append(self.splice_plan(ids, px.shape[0], tokens_at_layer(t0, r, self.v["num_hidden_layers"] - 1) - 1))
+        if samp is not None:
+            self._sampling_on()
         self.begin_batch(B, max_new_tokens, eos_id)
+        self._begin_sampled(samp, streams, B)
         for b, g, stride in prefill_groups([p["seq_len"] for p in plans], prefill_group, self.prompt_bucket):
             lens = [plans[b + i]["seq_len"] for i in range(g)]
             mixed = len(set(lens)) > 1                            # only with a bucket: lengths go to the device, rows beyond them are don't-care
@@ -660,7 +723,8 @@ class AuroraCapEngine:
         return lens, fin
 
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
-                       check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True):
+                       check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
+                       sampling: Optional[dict] = None, stream_of=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -673,7 +737,13 @@ class AuroraCapEngine:
         their own stream, restricted to `front_cus` CUs of every XCD, into the spare KV sequences while every slot keeps
         decoding (decode is HBM-bound, ViT + prefill MFMA-bound); a freed slot takes over a prepared clip's pages at the next
         check (`prefill_commit`).  front_graph (overlapped mode): each clip's front end is one hipGraph replay, captured per shape
-        bucket on first use (`_front_end_replay`); False = ~600 eager launches per clip.  Same ids either way."""
+        bucket on first use (`_front_end_replay`); False = ~600 eager launches per clip.  Same ids either way.
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions; a clip's stream is its index in `clips` (or
+        stream_of(index), called when the clip is about to get its slot), whatever slot it lands in and whenever (a re-filled slot
+        gets the new clip's record before its first token is picked)."""
+        samp = S.check_sampling(sampling)
+        if samp is not None:
+            self._sampling_on()
         B = self.max_batch if slots is None else slots
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"slots={B} for an engine built with max_batch={self.max_batch}")
@@ -683,7 +753,7 @@ class AuroraCapEngine:
             if self.spare_slots < 1:
                 raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph)
+                                                       front_graph, samp, stream_of)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -704,6 +774,8 @@ class AuroraCapEngine:
                         vis = self.vit_encode(px, r)
                         emb, L = self.project_splice(vis, list(ids))
                         self.slot_reset(s)
+                        if samp is not None:
+                            self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                         self.prefill(s, emb, L)                   # argument checks come before any enqueue: a rejection leaves the slot idle
                         owner[s] = idx
                     except (ValueError, IndexError, AssertionError, _lib.AuroraHipError) as e:
@@ -776,7 +848,8 @@ class AuroraCapEngine:
         fg._last.record(torch.cuda.current_stream(self.dev))
         return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"])
 
-    def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True):
+    def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
+                                   samp=None, stream_of=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -800,6 +873,8 @@ class AuroraCapEngine:
                         idx, seq, emb, L, ev = staged.popleft()
                         sD.wait_event(ev)
                         emb.record_stream(sD)
+                        if samp is not None:                      # the captured front end holds the stage only: the pick is the commit's
+                            self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                         if isinstance(L, tuple):                  # a bucketed front end: (stride, the graph's static lengths buffer)
                             self.prefill_commit(s, 1, seq, emb, L[0], seq_lens=L[1])
                         else:

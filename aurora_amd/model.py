@@ -9,7 +9,8 @@ lmms_eval/models/auroracap.py:500-509):
                               max_new_tokens=N)       # LongTensor [1, <= N]: new ids only
 
 keep their names, argument meaning and error behaviour (NotImplementedError for unknown modes,
-aurora.py:269-270).  Only greedy decoding exists on this path (`do_sample=False`, inference.py:91).
+aurora.py:269-270).  Decoding is greedy (`do_sample=False`, what inference.py:91 hard-codes) or seeded sampling
+(`do_sample=True`: temperature / top-k / top-p as aurora_amd.sampling defines them); beam search does not exist on this path.
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from typing import Optional
 import torch
 
 from .engine import AuroraCapEngine
+from .sampling import DEFAULT_TOP_K, check_sampling
 
 DEFAULT_IMAGE_TOKEN = "<image>"          # src/xtuner/xtuner/utils/constants.py:5
 IMAGE_TOKEN_INDEX = -200                 # constants.py:4
@@ -41,6 +43,19 @@ def build_prompt(prompt: str, num_images: int) -> str:
     return VICUNA_INSTRUCTION.format(input=" ".join([DEFAULT_IMAGE_TOKEN] * num_images) + "\n" + prompt, round=1)
 
 
+def generation_top_k(path: str) -> Optional[int]:
+    """`top_k` of the language model's generation_config.json under an xtuner-layout checkpoint directory, or None."""
+    import json
+    import os
+    for sub in ("llm", ""):
+        f = os.path.join(path, sub, "generation_config.json")
+        if os.path.isfile(f):
+            with open(f) as fh:
+                k = json.load(fh).get("top_k")
+            return None if k is None else int(k)
+    return None
+
+
 class AuroraEncoder:
     """visual_encoder handle (aurora.py:869-904): only the ratio knob and the r formula live on the host."""
 
@@ -61,15 +76,29 @@ class _LLM:
     def __init__(self, engine: AuroraCapEngine, eos_token_id: Optional[int]):
         self._e = engine
         self.eos_token_id = eos_token_id
+        self.generation_top_k = None          # generation_config.json's top_k, when the checkpoint has one (AuroraModel.from_pretrained)
         self.config = engine.l
 
     def generate(self, inputs_embeds: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.0, top_p: float = 1.0,
                  num_beams: int = 1, max_new_tokens: int = 2048, input_ids=None, position_ids=None, attention_mask=None,
-                 past_key_values=None, labels=None, eos_token_id="default", **unused) -> torch.Tensor:
+                 past_key_values=None, labels=None, eos_token_id="default", top_k="default", seed: int = 0, stream: int = 0,
+                 **unused) -> torch.Tensor:
+        """do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
+        sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
+        passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
+        ids are a function of (seed, stream) and the prompt alone.
+        top_k follows the transformers range the reference pins (<= 4.42), whose GenerationConfig defaults it to 50 - later
+        releases report None -; a `top_k` in the checkpoint's generation_config.json (`self.generation_top_k`) wins over that default,
+        an explicit argument over both; top_k=0 turns the filter off."""
         if inputs_embeds is None:
             raise ValueError("generate() on this path takes inputs_embeds (the output of model(data, mode='inference'))")
-        if do_sample or num_beams != 1:
-            raise NotImplementedError("only greedy decoding (do_sample=False, num_beams=1) is implemented on the MI355X path")
+        if num_beams != 1:
+            raise NotImplementedError("beam search is not implemented on the MI355X path (num_beams=1 only)")
+        sampling = None
+        if do_sample:
+            if top_k == "default":
+                top_k = DEFAULT_TOP_K if self.generation_top_k is None else self.generation_top_k
+            sampling = check_sampling(dict(temperature=temperature, top_p=top_p, top_k=top_k, seed=seed))
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
             raise ValueError(f"inputs_embeds must be [1, L, {self.config['hidden_size']}], got {tuple(inputs_embeds.shape)}")
         eos = self.eos_token_id if eos_token_id == "default" else eos_token_id
@@ -77,7 +106,7 @@ class _LLM:
         pad = torch.zeros((L + 31) // 32 * 32, d, dtype=torch.float16, device=self._e.dev)
         pad[:L] = inputs_embeds[0].to(device=self._e.dev, dtype=torch.float16)
         n = min(max_new_tokens, self._e.max_new_tokens)
-        ids = self._e.generate([pad], [L], n, eos_id=eos)[0]
+        ids = self._e.generate([pad], [L], n, eos_id=eos, **(dict(sampling=sampling, streams=[stream]) if sampling else {}))[0]
         return torch.tensor([ids], dtype=torch.long)
 
 
@@ -95,32 +124,39 @@ class AuroraModel:
         cfg, weights = load_auroracap(path)
         eng = AuroraCapEngine(cfg, weights, max_frames=max_frames, max_batch=max_batch, max_ctx=max_ctx,
                               max_new_tokens=max_new_tokens, **kw)
-        return cls(eng, cfg["llm"].get("eos_token_id", 2), slowfast=slowfast)
+        model = cls(eng, cfg["llm"].get("eos_token_id", 2), slowfast=slowfast)
+        model.llm.generation_top_k = generation_top_k(path)
+        return model
 
-    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default"):
+    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
-        identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio."""
+        identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions, clip i drawing with stream streams[i] (default: i)."""
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
         n = min(max_new_tokens, self.engine.max_new_tokens)
         for c0 in range(0, len(clips), B):
             group = [(px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips[c0:c0 + B]]
-            out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos))
+            st = range(c0, c0 + len(group)) if streams is None else list(streams)[c0:c0 + len(group)]
+            kw = dict(sampling=sampling, streams=st) if sampling is not None else {}
+            out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
-                       overlap=None):
+                       overlap=None, sampling=None, stream_of=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): yields (index, new-token ids) as captions
         finish (EOS or max_new_tokens), re-filling freed KV slots with the next clips.  Per-clip results equal the
         one-at-a-time calls.  overlap (default: on for an engine with spare KV sequences): the next clips' front ends run
-        ahead on a CU-masked stream while the slots decode (AuroraCapEngine.caption_stream)."""
+        ahead on a CU-masked stream while the slots decode (AuroraCapEngine.caption_stream).
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip k draws with stream stream_of(k) (default: k)."""
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         n = min(max_new_tokens, self.engine.max_new_tokens)
         it = ((px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips)
         yield from self.engine.caption_stream(it, self.visual_encoder.visual_token_merge_ratio, n, eos, check_every=check_every,
-                                              on_error=on_error, overlap=overlap)
+                                              on_error=on_error, overlap=overlap,
+                                              **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}))
 
     def __call__(self, data: dict, data_samples=None, mode: str = "loss"):
         return self.forward(data, data_samples, mode)

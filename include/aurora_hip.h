@@ -181,6 +181,17 @@ int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t se
 int aur_llm_prefill_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
 int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
 int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
+/* Sampled generation: with option "sampling" = 1 (aur_set_option) the token pick of every prefill / commit /
+ * decode step draws from the slot's temperature / top-k / top-p distribution instead of taking the first maximum.  The draw for
+ * (seed, stream, token index) is word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (token index, stream, 0, 0): a pure
+ * function of those and of the logits row, whatever the batch, slot, bank or launch form.  temperature == 0 on a slot = greedy. */
+typedef struct aur_sampling { float temperature, top_p; int32_t top_k; uint32_t stream; uint64_t seed; } aur_sampling;
+/* per-slot parameters of the selected bank, copied device-to-device from caller-owned DEVICE memory when the work runs (like
+ * seq_lens_dev): enqueue-only, recordable with aur_graph_begin; a capture freezes the pointer, not the values.  They hold until
+ * overwritten; aur_begin_batch sets every slot to greedy (temperature 0).  Must be ordered before the prefill / commit that
+ * produces the slot's first token.  temperature < 0 (-> 0), top_p outside (0, 1] (<= 0: the maximum alone; > 1: off), top_k < 0
+ * (-> off) are clamped by the kernel (the host cannot see them); the Python layer validates where the values are known. */
+int aur_slot_sampling(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_sampling* params_dev, void* stream);
 /* Run `steps` decode steps for slots [0, batch): one new token per unfinished slot per step. */
 int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream);
 /* Synchronises the stream and copies results to host: ids [batch * max_new_tokens], lens [batch]. */
@@ -261,12 +272,21 @@ int aur_vit_layer(aur_ctx* ctx, int32_t layer, const void* x, const float* size,
 /* Copy the last-position logits of the most recent prefill / decode step into dst_dev: fp32 [batch, vocab]. */
 int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
 
+/* The sampled pick alone on caller rows (parity tests).  logits fp32 [rows, vocab] device (16-byte aligned); params_dev [rows];
+ * n_dev int32 [rows] (the token index that goes into the counter); tokens_out int32 [rows]; kept_out int32 [rows] or NULL (the size
+ * of the kept set). */
+int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const aur_sampling* params_dev,
+                    const int32_t* n_dev, int32_t* tokens_out, int32_t* kept_out, void* stream);
+
 /* Tuning knobs.  Invalidate the captured decode graphs (of every bank): "decode_fused_reduce" 0 (default: the split-K residual projections are followed
  * by a reduce launch) / 1 (the last-arriving split reduces inside the kernel; bitwise the same), "dec_attn_local" 1 (default: on engines
  * of 8-15 slots x 32 heads the splits of a (sequence, head) are the waves of one attention workgroup, joined through LDS) / 0
  * (decode_attn_combine_kernel joins them; bitwise the same), "dec_attn_pps" pages per decode-attention split, "skinny_row_split_min_k"
  * (K from which the residual projections of an engine of <= 64 slots take the split-K structure), "decode_stamp_layer" (see
- * aur_decode_stamps_read).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
+ * aur_decode_stamps_read), "sampling" 0 (default: the pick is argmax_advance_kernel) / 1 (sample_advance_kernel with the slots'
+ * aur_sampling records; the kernel choice is frozen inside captured graphs - the decode step's, which this call drops, and a CALLER's
+ * capture that holds a prefill / commit, which the caller re-captures), "sample_stage" 1 (default: the sampler stages its logits
+ * row in LDS when it fits) / 0 (re-reads it from L2; same tokens).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
  * launch) / 0 (its own launch; bitwise the same); "prefill_prune_last" 1 (default) / 0: the last layer of a prefill computes K / V for
  * every position and the rest for each sequence's last 128 rows only - nothing else is read after it; bitwise the same logits and K / V;
  * "decode_half_grid" 1 / 0 (one graph is kept per setting): the next aur_llm_decode calls go to a stream that owns half of the CUs, so
@@ -282,7 +302,7 @@ int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
  * LDS above), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
 int aur_set_option(aur_ctx* ctx, const char* name, int64_t value);
 /* Time one kernel of the LLM path in isolation on the current generation state (after aur_llm_prefill):
- * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, pre_norm, pre_qkv, pre_attn,
+ * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), pre_norm, pre_qkv, pre_attn,
  * pre_o, pre_gateup, pre_down}; mean microseconds per launch over `iters` launches cycling through the layers. */
 int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, double* us_out, void* stream);
 

@@ -29,20 +29,26 @@ def build_parser() -> argparse.ArgumentParser:
             ("visual_input", str, "output.png", "video (.mp4) or image (.png / .jpg) file"),
             ("num_frm", int, 8, "frames sampled uniformly from a video"),
             ("token_kept_ratio", float, 0.8, "fraction of visual tokens kept by the per-layer token merge"),
-            ("temperature", float, 0.0, "sampling temperature (greedy only on this path)"),
-            ("top_p", float, 1.0, "nucleus mass (unused: greedy)"),
+            ("temperature", float, 0.0, "sampling temperature (takes effect with --do_sample; without it generation is greedy)"),
+            ("top_p", float, 1.0, "nucleus mass kept by top-p sampling (takes effect with --do_sample)"),
             ("num_beams", int, 1, "beam count (only 1 is implemented)"),
             ("max_new_tokens", int, 2048, "generation budget")):
         parser.add_argument("--" + flag, type=typ, default=default, help=text)
     parser.add_argument('--host_preprocess', action='store_true', help='resize/normalise on the host with CLIPImageProcessor (PIL) instead of the HIP input stage')
     parser.add_argument('--synthetic', action='store_true', help='seeded synthetic weights / clip / prompt ids (no checkpoint needed)')
+    # the reference CLI hard-codes do_sample=False (inference.py:91); sampling is this path's own switch
+    parser.add_argument('--do_sample', action='store_true', help='seeded sampling with --temperature (required, > 0) / --top_p / --top_k instead of greedy decoding')
+    parser.add_argument('--top_k', type=int, default=50, help='with --do_sample: keep the k most likely tokens (0 = off)')
+    parser.add_argument('--seed', type=int, default=0, help='with --do_sample: seed of the counter-based generator (same seed, same caption)')
     return parser
 
 
 def main():
     args = build_parser().parse_args()
+    if args.do_sample and not args.temperature > 0:
+        sys.exit("error: --do_sample needs --temperature > 0 (the reference CLI's default temperature, 0.0, is kept: it means greedy)")
     if args.num_beams != 1:
-        sys.exit("error: only greedy decoding is implemented on the MI355X path (--num_beams 1)")
+        sys.exit("error: beam search is not implemented on the MI355X path: generation is greedy or, with --do_sample, sampled (--num_beams 1)")
 
     from aurora_amd.model import AuroraModel, build_prompt, process_text
 
@@ -104,8 +110,9 @@ def main():
 
     model.visual_encoder.reset_tome_r(args.token_kept_ratio)
     output = model(data, mode="inference")
-    cont = model.llm.generate(**output, do_sample=False, temperature=args.temperature, top_p=args.top_p,
-                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens)
+    sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
+    cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
+                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample)
     if tokenizer is None:
         print(cont[0].tolist())
     else:
