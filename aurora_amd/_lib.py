@@ -79,6 +79,10 @@ SIGNATURES = {
     "aur_llm_prefill_batch_var": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
     "aur_llm_prefill_stage_var": (C.c_int, [_P, _I, _I, _P, _I, _P, _P]),
     "aur_llm_prefill_commit_var": (C.c_int, [_P, _I, _I, _I, _P, _I, _P, _P]),
+    "aur_kv_copy_prefix": (C.c_int, [_P, _I, _I, _I, _I, _P]),
+    "aur_llm_extend_batch_var": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P]),
+    "aur_llm_extend_stage_var": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P]),
+    "aur_llm_extend_commit_var": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "aur_llm_decode": (C.c_int, [_P, _I, _P]),
     "aur_get_outputs": (C.c_int, [_P, _IP, _IP, _P]),
     "aur_unfinished": (C.c_int, [_P, _IP, _P]),

@@ -78,7 +78,8 @@ __device__ __forceinline__ void advance_tail(int b, int row, int tok, const half
             }
             if (tok == eos_id || n + 1 >= max_new) finished[b] = 1;     // EOS, or the output row is full
         }
-        if (set_pos_lens) pos[b] = var_len(set_pos_lens, row, len_cap);       // a variable-length prefill: each slot's own length
+        // a variable-length prefill: each slot's own length, behind the set_pos positions it already held (0, or an extend's pos0)
+        if (set_pos_lens) pos[b] = set_pos + var_len(set_pos_lens, row, len_cap);
         else if (set_pos >= 0) pos[b] = set_pos;
         // a finished (or idle) slot stops advancing: it keeps recomputing one position inside its own pages, so extra
         // decode steps (other slots still running, continuous batching) can never walk it past its KV allocation

@@ -47,8 +47,9 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
     int t = a.t, q_pos0 = a.q_pos0;
     int t_pad = 0x7fffffff;                         // query positions from here on are padding rows, stored as zeros (never, without lengths)
     if (a.seq_lens) {
-        t = t_pad = var_len(a.seq_lens, seq, a.len_cap);
-        if (a.q_tail) q_pos0 = var_row0(t, a.rows_per_seq);
+        const int len = var_len(a.seq_lens, seq, a.len_cap);
+        t = t_pad = a.len_pos0 + len;               // keys [0, len_pos0) were there before this pass (an extend; 0 for a prefill)
+        if (a.q_tail) q_pos0 = a.len_pos0 + var_row0(len, a.rows_per_seq);
         if (q_pos0 + qb * 128 >= t) {               // the whole query block is padding: nothing to compute, its output rows are zeros
             const h4 z = h4{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
             for (int qt = 0; qt < 2; ++qt) {

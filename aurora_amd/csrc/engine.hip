@@ -986,7 +986,10 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
 // so that aur_microbench can time each of them in isolation.
 // lens != nullptr (the _var entry points): `seq_len` is the row stride of the sequences, a multiple of 32, and sequence i holds
 // lens[i] rows (device memory, read by the attention kernel); the other kernels of a layer work row by row and need no length.
-static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr) {
+// pos0 > 0 (aur_llm_extend_*): the rows are positions [pos0, pos0 + lens[i]) of sequences whose pages already hold [0, pos0) - RoPE and the
+// page write at pos0 + row, queries at pos0 + row over keys [0, pos0 + lens[i]); everything else is the same launch.
+static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr,
+                         int pos0 = 0) {
     const aur_config& g = ctx->cfg;
     const LlmLayerW& w = ctx->ll[l];
     const int d = g.llm_hidden, Mseq = rup(seq_len, 32), M = nseq * Mseq;
@@ -995,14 +998,14 @@ static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, hal
         GemmArgs q{};
         q.A = ctx->l_xn; q.lda = d; q.W = w.qkv_w; q.bias = nullptr; q.M = M; q.Npad = ctx->l_qkv_npad; q.K = d;
         q.rows_per_seq = Mseq; q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = 0; q.seq0 = slot; q.tag = GT_LLM_QKV;
+        q.rope = ctx->l_rope; q.pos0 = pos0; q.seq0 = slot; q.tag = GT_LLM_QKV;
         CK(ctx_gemm(ctx, q, EPI_QKV, s));
     }
     if (which & 4) {
         AttnArgs at{};
         at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = Mseq; at.t = seq_len;
         at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = ctx->l_attn; at.ldo = d; at.hd = ctx->l_hd;
-        at.seq_lens = lens; at.len_cap = Mseq;
+        at.seq_lens = lens; at.len_cap = Mseq; at.q_pos0 = pos0; at.len_pos0 = pos0;
         CK(launch_attention(at, s));
     }
     if (which & 8) {
@@ -1037,7 +1040,9 @@ static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, hal
 // lens != nullptr: the block of sequence i is the 128 rows that end at rup(lens[i], 32) - row0 is per sequence, so the gathers and the
 // scatter are one small kernel that reads the lengths, and the query GEMM's RoPE position and the attention's q_pos0 derive from them
 // on the device (GemmArgs.tail_lens, AttnArgs.q_tail).  A sequence of <= 128 rows has row0 = 0: its block is the unpruned computation.
-static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr) {
+// pos0 > 0 (aur_llm_extend_*): row0 stays relative to the rows of this pass; positions are pos0 + row as in prefill_layer.
+static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr,
+                              int pos0 = 0) {
     const aur_config& g = ctx->cfg;
     const LlmLayerW& w = ctx->ll[l];
     const int d = g.llm_hidden, mlp = g.llm_mlp, Mseq = rup(seq_len, 32), M = nseq * Mseq, LB = 128, Mc = nseq * LB, row0 = Mseq - LB;
@@ -1051,7 +1056,7 @@ static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x
         GemmArgs q{};
         q.A = ctx->l_xn; q.lda = d; q.W = w.qkv_w + (int64_t)(d / 16) * (d / 32) * AUR_FRAG_HALVES; q.M = M; q.Npad = ctx->l_qkv_npad - d; q.K = d;
         q.rows_per_seq = Mseq; q.q_cols = 0; q.k_cols = d; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = 0; q.seq0 = slot; q.tag = GT_LLM_QKV;
+        q.rope = ctx->l_rope; q.pos0 = pos0; q.seq0 = slot; q.tag = GT_LLM_QKV;
         CK(ctx_gemm(ctx, q, EPI_QKV, s));
     }
     if (lens) CK(launch_tail_rows(ctx->l_xn, x, xn_c, x_c, d, nseq, Mseq, LB, lens, 1, s));
@@ -1063,14 +1068,14 @@ static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x
         GemmArgs q{};
         q.A = xn_c; q.lda = d; q.W = w.qkv_w; q.M = Mc; q.Npad = d; q.K = d;
         q.rows_per_seq = LB; q.q_cols = d; q.k_cols = 0; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = row0; q.seq0 = slot; q.tag = GT_OTHER; q.tail_lens = lens; q.tail_cap = Mseq;
+        q.rope = ctx->l_rope; q.pos0 = lens ? pos0 : pos0 + row0; q.seq0 = slot; q.tag = GT_OTHER; q.tail_lens = lens; q.tail_cap = Mseq;
         CK(ctx_gemm(ctx, q, EPI_QKV, s));
     }
     {
         AttnArgs at{};
         at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = LB; at.t = seq_len;
-        at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = attn_c; at.ldo = d; at.hd = ctx->l_hd; at.q_pos0 = row0;
-        at.seq_lens = lens; at.len_cap = Mseq; at.q_tail = 1;
+        at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = attn_c; at.ldo = d; at.hd = ctx->l_hd; at.q_pos0 = pos0 + row0;
+        at.seq_lens = lens; at.len_cap = Mseq; at.q_tail = 1; at.len_pos0 = pos0;
         CK(launch_attention(at, s));
     }
     {
@@ -1110,7 +1115,8 @@ static int var_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds,
 // lens != nullptr: seq_len is the stride (checked by var_args) and the rows [lens[i], stride) of every sequence are cleared first: whatever
 // the caller left there, they are zeros in every layer (an all-zero row stays zero through norm, projections, RoPE and the MLP, and the
 // attention kernel stores zeros for it), and so are the K / V written for them.
-static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who, const int32_t* lens = nullptr) {
+static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who, const int32_t* lens = nullptr,
+                          int pos0 = 0) {
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
@@ -1123,8 +1129,8 @@ static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int se
     for (int l = 0; l < g.llm_layers; ++l) {
         // the compact scratch of the pruned last layer must fit l_h: nseq * 128 * (3 d + mlp) <= nseq * Mseq * mlp (and LB < Mseq)
         const bool prune = ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
-        int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s, lens)
-                       : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s, lens);
+        int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0)
+                       : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0);
         if (rc) return rc;
     }
     return AUR_OK;
@@ -1132,14 +1138,14 @@ static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int se
 // First tokens of slots [slot0, slot0 + nseq) from the last prompt rows of `embeds` (the final hidden states `prefill_layers` left
 // there): residual fragments + sum(x^2) - the lm_head applies the (folded) final RMSNorm itself -, logits, argmax, bookkeeping.
 static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* stage = "prefill",
-                                const int32_t* lens = nullptr) {
+                                const int32_t* lens = nullptr, int pos0 = 0) {
     const aur_config& g = ctx->cfg;
     const int d = g.llm_hidden, Mseq = rup(seq_len, 32);
     if (ctx->prof) kev_begin(ctx->kev[3], s);
     // the last prompt row of every sequence and its decode position: seq_len - 1 / seq_len, or per sequence from the device lengths
     CK(launch_xfrag_norm((half_t*)embeds + (lens ? 0 : (int64_t)(seq_len - 1) * d), (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->bank().d_x,
                          ctx->bank().s_ssq_mlp, s, 16, lens, Mseq));
-    int rc = lm_head_and_advance(ctx, slot0, nseq, 0, seq_len, s, lens, Mseq);
+    int rc = lm_head_and_advance(ctx, slot0, nseq, 0, lens ? pos0 : seq_len, s, lens, Mseq);      // decode position: seq_len, or pos0 + len_i
     if (ctx->prof) kev_end(ctx->kev[3], s);       // closed on the error path too: the event ring and the roctx nesting stay balanced
     stage_end(ctx, stage, s);
     return rc;
@@ -1175,14 +1181,16 @@ __global__ void ptab_swap_kernel(int32_t* __restrict__ pt, int a0, int b0, int n
     *pb = t;
 }
 
-static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream, const int32_t* lens) {
+static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream, const int32_t* lens,
+                          int pos0 = 0) {
     const aur_ctx::Bank& K = ctx->bank();
-    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_llm_prefill_commit: no active batch");
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slots [%d, %d) outside the batch of %d", slot0, slot0 + nseq, K.batch);
-    if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: KV sequences [%d, %d) outside [0, %d)", seq0, seq0 + nseq, ctx->kv_seqs);
-    if (seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit: slot and sequence ranges overlap");
+    const char* who = pos0 ? "aur_llm_extend_commit_var" : (lens ? "aur_llm_prefill_commit_var" : "aur_llm_prefill_commit");
+    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch", who);
+    if (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: slots [%d, %d) outside the batch of %d", who, slot0, slot0 + nseq, K.batch);
+    if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d)", who, seq0, seq0 + nseq, ctx->kv_seqs);
+    if (seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq) return aur_fail(ctx, AUR_ERR_ARG, "%s: slot and sequence ranges overlap", who);
     if (lens) {
-        if (int rc = var_args(ctx, "aur_llm_prefill_commit_var", nseq, embeds, seq_len, lens)) return rc;
+        if (int rc = var_args(ctx, who, nseq, embeds, seq_len, lens)) return rc;
     } else if (seq_len < 1 || seq_len + K.max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, ctx->cfg.max_ctx);
     hipStream_t s = (hipStream_t)stream;
     stage_begin(ctx, "prefill_commit", s);
@@ -1195,7 +1203,7 @@ static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq
     CK(hipMemsetAsync(K.s_fin + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit", lens);
+    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit", lens, pos0);
 }
 extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
     return prefill_commit(ctx, slot0, nseq, seq0, embeds, seq_len, stream, nullptr);
@@ -1225,6 +1233,91 @@ extern "C" int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nse
     if (int rc = var_args(ctx, "aur_llm_prefill_stage_var", nseq, embeds, stride, seq_lens_dev)) return rc;
     if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, (hipStream_t)stream, "aur_llm_prefill_stage_var", seq_lens_dev)) return rc;
     stage_end(ctx, "prefill", (hipStream_t)stream);
+    return AUR_OK;
+}
+
+// ---- prefill that starts at a position > 0: the rows of this pass are positions [pos0, pos0 + len_i) of sequences whose pages already hold
+// [0, pos0) (an earlier prefill, or aur_kv_copy_prefix from a sequence with the same leading rows).  The layer stack is the one above
+// with pos0 added to every position; the host checks what it can see, the lengths stay on the device.
+static int extend_pos_args(aur_ctx* ctx, const char* who, int pos0, int stride) {
+    if (pos0 < ctx->cfg.page_tokens || pos0 % ctx->cfg.page_tokens)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d is not a positive multiple of the %d-token page", who, pos0, ctx->cfg.page_tokens);
+    if ((int64_t)pos0 + stride > ctx->l_ctx_pad)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d + stride %d exceeds the %d positions of a sequence's KV pages", who, pos0, stride, ctx->l_ctx_pad);
+    return AUR_OK;
+}
+static int extend_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds, int pos0, int stride, const int32_t* lens) {
+    if (int rc = var_args(ctx, who, nseq, embeds, stride, lens)) return rc;
+    return extend_pos_args(ctx, who, pos0, stride);
+}
+extern "C" int aur_llm_extend_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride,
+                                        const int32_t* new_lens_dev, void* stream) {
+    const int B = ctx->bank().batch;
+    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_batch_var: slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
+    if (int rc = extend_args(ctx, "aur_llm_extend_batch_var", nseq, embeds, pos0, stride, new_lens_dev)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = prefill_layers(ctx, slot0, nseq, embeds, stride, s, "aur_llm_extend_batch_var", new_lens_dev, pos0)) return rc;
+    return prefill_first_tokens(ctx, slot0, nseq, embeds, stride, s, "prefill", new_lens_dev, pos0);
+}
+extern "C" int aur_llm_extend_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride,
+                                        const int32_t* new_lens_dev, void* stream) {
+    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_stage_var: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", seq0, seq0 + nseq, ctx->kv_seqs);
+    if (int rc = extend_args(ctx, "aur_llm_extend_stage_var", nseq, embeds, pos0, stride, new_lens_dev)) return rc;
+    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, (hipStream_t)stream, "aur_llm_extend_stage_var", new_lens_dev, pos0)) return rc;
+    stage_end(ctx, "prefill", (hipStream_t)stream);
+    return AUR_OK;
+}
+extern "C" int aur_llm_extend_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t pos0, int32_t stride,
+                                         const int32_t* new_lens_dev, void* stream) {
+    if (!new_lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_commit_var: null new_lens_dev");
+    if (int rc = extend_pos_args(ctx, "aur_llm_extend_commit_var", pos0, stride)) return rc;      // stride / nseq / embeds: var_args, in prefill_commit
+    return prefill_commit(ctx, slot0, nseq, seq0, embeds, stride, stream, new_lens_dev, pos0);
+}
+
+// K and V of positions [0, tokens) of KV sequence src_seq -> sequences [dst_seq0, dst_seq0 + ndst) of the selected bank, every layer.
+// One workgroup per (chunk, page, layer): the page ids come from the page table when the kernel runs (whatever row exchanges earlier
+// commits queued on the stream), each 16-byte piece of the source page is loaded once and stored ndst times.  The pages stream through
+// (33 pages x 32 layers x 1 MiB per child at 7B, several times the L2s): non-temporal stores, as for the large GEMM outputs.
+#define KVC_THREADS 256
+#define KVC_PIECES 4                                         /* 16-byte pieces per thread: 16 KiB per workgroup */
+__global__ __launch_bounds__(KVC_THREADS) void kv_copy_prefix_kernel(half_t* __restrict__ pool, int64_t layer_halves, int64_t page_halves,
+                                                                      const int32_t* __restrict__ ptab, int max_pages, int src_seq, int dst_seq0,
+                                                                      int ndst) {
+    const int page = blockIdx.y, layer = blockIdx.z;
+    const int64_t pieces = page_halves >> 3;                 // a page is whole 1 KiB fragments
+    const int64_t p0 = (int64_t)blockIdx.x * (KVC_THREADS * KVC_PIECES) + threadIdx.x;
+    half_t* const lbase = pool + (int64_t)layer * layer_halves;
+    const h8* src = (const h8*)(lbase + (int64_t)ptab[(int64_t)src_seq * max_pages + page] * page_halves);
+    h8 v[KVC_PIECES];
+#pragma unroll
+    for (int i = 0; i < KVC_PIECES; ++i) {
+        const int64_t p = p0 + i * KVC_THREADS;
+        if (p < pieces) v[i] = src[p];
+    }
+    for (int j = 0; j < ndst; ++j) {
+        h8* dst = (h8*)(lbase + (int64_t)ptab[(int64_t)(dst_seq0 + j) * max_pages + page] * page_halves);
+#pragma unroll
+        for (int i = 0; i < KVC_PIECES; ++i) {
+            const int64_t p = p0 + i * KVC_THREADS;
+            if (p < pieces) __builtin_nontemporal_store(v[i], dst + p);
+        }
+    }
+}
+extern "C" int aur_kv_copy_prefix(aur_ctx* ctx, int32_t src_seq, int32_t dst_seq0, int32_t ndst, int32_t tokens, void* stream) {
+    if (!ctx->finalized || ctx->ll.empty() || !ctx->kvpool) return aur_fail(ctx, AUR_ERR_STATE, "aur_kv_copy_prefix: language weights not finalized");
+    const int pt = ctx->cfg.page_tokens;
+    if (tokens < pt || tokens % pt || tokens > ctx->l_ctx_pad)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_kv_copy_prefix: tokens %d is not a positive multiple of the %d-token page within the %d positions of a sequence", tokens, pt, ctx->l_ctx_pad);
+    if (src_seq < 0 || src_seq >= ctx->kv_seqs || ndst < 1 || dst_seq0 < 0 || (int64_t)dst_seq0 + ndst > ctx->kv_seqs)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_kv_copy_prefix: source %d or destinations [%d, %d) outside [0, %d) (max_batch + spare_slots)", src_seq, dst_seq0, dst_seq0 + ndst, ctx->kv_seqs);
+    if (src_seq >= dst_seq0 && src_seq < dst_seq0 + ndst)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_kv_copy_prefix: source %d inside the destinations [%d, %d)", src_seq, dst_seq0, dst_seq0 + ndst);
+    const int64_t pieces = ctx->l_page_halves >> 3;
+    const dim3 grid((unsigned)((pieces + KVC_THREADS * KVC_PIECES - 1) / (KVC_THREADS * KVC_PIECES)), tokens / pt, ctx->cfg.llm_layers);
+    hipLaunchKernelGGL(kv_copy_prefix_kernel, grid, dim3(KVC_THREADS), 0, (hipStream_t)stream, (half_t*)ctx->kvpool, ctx->l_layer_halves,
+                       ctx->l_page_halves, ctx->bank().ptab, ctx->l_max_pages, src_seq, dst_seq0, ndst);
+    CK(hipGetLastError());
     return AUR_OK;
 }
 

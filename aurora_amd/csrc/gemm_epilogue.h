@@ -57,14 +57,14 @@ __device__ __forceinline__ void qkv_epilogue_qk(const GemmArgs& a, f4 (&acc)[TN]
     // (rows_per_seq, pos0, the page size and mb are multiples of 16; M is a multiple of rows_per_seq): sequence, page and fragment row
     // are wave-uniform - scalar divisions, a scalar page-table load - and a lane adds only its own 16 bytes (lane * 8 halves).
     int tokb[TM];                                       // first token of the row block in its sequence (uniform)
-    int posb[TM];                                       // its position: pos0 + tokb, pos0 per sequence under a.tail_lens (uniform)
+    int posb[TM];                                       // its position: pos0 + tokb, plus the sequence's own row0 under a.tail_lens (uniform)
     int64_t row_off[TM];                                // halves from the Q buffer / the layer's page pool, without the (head, block) term (uniform)
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
         const int mrow = min(mb + u * 16, a.M - 16);   // row blocks past M: the last real block's entries are read, nothing is stored
         const int seq = mrow / a.rows_per_seq;
         tokb[u] = mrow - seq * a.rows_per_seq;
-        posb[u] = (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : a.pos0) + tokb[u];
+        posb[u] = a.pos0 + (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : 0) + tokb[u];
         if (is_q) row_off[u] = (((int64_t)seq * kv.heads) * T16 + (tokb[u] >> 4)) * kv.kblk * AUR_FRAG_HALVES;
         else {
             const int pos = posb[u];
@@ -154,7 +154,7 @@ __device__ __forceinline__ void qkv_epilogue_v(const GemmArgs& a, f4 (&acc)[TN][
     for (int pu = 0; pu < TM / 2; ++pu) {
         const int mrow = min(mb + pu * 32, (a.M - 1) & ~31);          // row blocks past M: the last real block's page (nothing is stored)
         const int seq = mrow / a.rows_per_seq;
-        tok_of[pu] = (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : a.pos0) + mrow % a.rows_per_seq;   // position
+        tok_of[pu] = a.pos0 + (a.tail_lens ? var_row0(var_len(a.tail_lens, seq, a.tail_cap), a.rows_per_seq) : 0) + mrow % a.rows_per_seq;   // position
         pid[pu] = a.seq0 + seq;
     }
     if (kv.page_table) {

@@ -26,10 +26,11 @@ struct GemmArgs {
     half_t* Qf;             // Q fragments [seq][head][tok16][kblk][FRAG]
     KvLayout kv;            // K fragments / V^T fragments destination
     const float2* rope;     // [pos][hd/2] (cos, sin) or nullptr
-    int pos0;               // position of row 0 of each sequence (multiple of 32)
+    int pos0;               // position of row 0 of each sequence (multiple of 32); > 0: a tail (pruned last layer) or an extend pass
     int seq0;               // first sequence's row in the page table
     const int32_t* tail_lens;  // non-null (the pruned last layer of a variable-length prefill): sequence i's rows are the rows_per_seq rows that
-    int tail_cap;              // end at round_up(len_i, 32), so its pos0 is var_row0(var_len(tail_lens, i, tail_cap), rows_per_seq), not `pos0`
+    int tail_cap;              // end at round_up(len_i, 32), so its first row's position is `pos0` (the position of the pass's row 0: 0, or an
+                               // extend's pos0) + var_row0(var_len(tail_lens, i, tail_cap), rows_per_seq)
     // ---- per-ctx tuning knobs (aur_set_option; filled by the engine at every launch - nothing is process-global)
     int gemm_mode;          // 0: 128x128 kernel only, 1: auto, 2: force 256x256 when Npad % 256 == 0
     int max_wgs;            // 256x256 kernel: > 0 = at most this many persistent workgroups (= CUs); 0 = one per CU
@@ -78,7 +79,9 @@ struct AttnArgs {
                             // sequence's first token; > 0 = it holds only a tail of the sequence (the pruned last prefill layer)
     const int32_t* seq_lens;   // non-null: valid keys / queries of sequence i = var_len(seq_lens, i, len_cap) instead of `t` (device memory);
     int len_cap;               // query rows at or beyond a sequence's length are stored as zeros
-    int q_tail;                // with seq_lens: 1 = q_pos0 of sequence i is var_row0(len_i, rows_per_seq) (the pruned last layer)
+    int q_tail;                // with seq_lens: 1 = q_pos0 of sequence i is len_pos0 + var_row0(len_i, rows_per_seq) (the pruned last layer)
+    int len_pos0;              // with seq_lens: positions the sequence held before this pass (aur_llm_extend_*; 0 = a prefill) - the lengths count
+                               // the rows of the pass, so valid keys = len_pos0 + len_i, and q_pos0 of an untailed pass is len_pos0 (set by the caller)
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 

@@ -79,18 +79,68 @@ def prefill_groups(seq_lens: Sequence[int], prefill_group: int, bucket: int = 0)
     return out
 
 
-def check_seq_lens(seq_lens: Sequence[int], stride: int, max_new: int, max_ctx: int) -> List[int]:
+def check_seq_lens(seq_lens: Sequence[int], stride: int, max_new: int, max_ctx: int, pos0: int = 0) -> List[int]:
     """The host-side half of the variable-length prefill's contract (the kernels only clamp): 1 <= len <= stride, stride a multiple
-    of 32, len + max_new <= max_ctx."""
+    of 32, pos0 + len + max_new <= max_ctx (pos0 > 0: the lengths of an `extend_*` pass, which starts at that position)."""
     lens = [int(x) for x in seq_lens]
     if stride < 32 or stride % 32:
         raise ValueError(f"stride {stride} is not a positive multiple of 32")
     for x in lens:
         if not 1 <= x <= stride:
             raise ValueError(f"sequence length {x} outside [1, stride {stride}]")
-        if x + max_new > max_ctx:
-            raise ValueError(f"prompt of {x} positions + {max_new} new tokens exceeds max_ctx {max_ctx}")
+        if pos0 + x + max_new > max_ctx:
+            raise ValueError(f"prompt of {pos0 + x} positions + {max_new} new tokens exceeds max_ctx {max_ctx}")
     return lens
+
+
+# ---- shared visual prefixes: several prompts about one clip agree on every row up to and including the last visual token
+FORK_TOKENS = 64              # a fork lies on a KV page boundary: whole pages are copied, the rest is prefilled (`extend_*`)
+
+
+def _row_sources(plan: dict) -> np.ndarray:
+    """What each row of a spliced prompt is made of: visual row k (in marker order) -> -(k + 1), a text row -> its token id."""
+    def host(a):
+        return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    src = np.zeros(int(plan["seq_len"]), np.int64)
+    vr = host(plan["vis_rows"]).astype(np.int64)
+    src[vr] = -(np.arange(len(vr), dtype=np.int64) + 1)
+    tr, ti = host(plan["text_rows"]).astype(np.int64), host(plan["text_ids"]).astype(np.int64)
+    src[tr[tr >= 0]] = ti[tr >= 0]
+    return src
+
+
+def shared_prefix_rows(plan_a: dict, plan_b: dict) -> int:
+    """Leading rows of two splice plans (`splice_rows`) that are identical: the same visual row index in both, or the same text id
+    in both.  Says nothing about the visual rows' CONTENTS - the caller's share key does."""
+    a = plan_a["row_src"] if "row_src" in plan_a else _row_sources(plan_a)
+    b = plan_b["row_src"] if "row_src" in plan_b else _row_sources(plan_b)
+    n = min(len(a), len(b))
+    diff = np.nonzero(a[:n] != b[:n])[0]
+    return int(diff[0]) if len(diff) else n
+
+
+def fork_point(rows: int) -> int:
+    """The position a sibling prompt forks off at: `rows` shared rows rounded down to whole KV pages.  0 = no sharing."""
+    return max(int(rows), 0) // FORK_TOKENS * FORK_TOKENS
+
+
+def _vis_end(plan: dict) -> int:
+    """rows up to and including a plan's last visual row"""
+    if "vis_end" in plan:
+        return plan["vis_end"]
+    return int(max(plan["vis_rows"])) + 1 if len(plan["vis_rows"]) else 0
+
+
+def share_fork(parent: dict, child: dict) -> int:
+    """Where `child` may fork off `parent`'s KV sequence (both plans of the SAME visual input), or 0 when it must take the unshared
+    path: the plans diverge before the visual rows end, or less than a page is shared.  The child keeps at least one row of its own
+    (identical prompts fork a page early: the first token comes from the child's own last row)."""
+    if parent["nvis"] != child["nvis"] or parent["used"] != child["used"] or child["nvis"] < 1:
+        return 0
+    shared = shared_prefix_rows(parent, child)
+    if shared < max(_vis_end(parent), _vis_end(child)):
+        return 0
+    return fork_point(min(shared, int(child["seq_len"]) - 1))
 
 
 def splice_rows(input_ids: Sequence[int], frames: int, n_kept, strict: bool = False, ntext_cap: Optional[int] = None) -> dict:
@@ -118,7 +168,10 @@ def splice_rows(input_ids: Sequence[int], frames: int, n_kept, strict: bool = Fa
         text_ids += [0] * (ntext_cap - ntext)
         text_rows += [-1] * (ntext_cap - ntext)
     vr = np.concatenate(vis_rows) if vis_rows else np.zeros(0, np.int64)
-    return dict(seq_len=row, used=len(vis_rows), n_kept=n_kept, nvis=int(sum(counts[:len(vis_rows)])), ntext=ntext, ntext_cap=ntext_cap,
+    src = np.zeros(row, np.int64)                      # per row: visual row k -> -(k + 1), text -> its id (`shared_prefix_rows`)
+    src[vr] = -(np.arange(len(vr), dtype=np.int64) + 1)
+    src[np.asarray(text_rows[:ntext], np.int64)] = np.asarray(text_ids[:ntext], np.int64)
+    return dict(row_src=src, vis_end=int(vr.max()) + 1 if len(vr) else 0, seq_len=row, used=len(vis_rows), n_kept=n_kept, nvis=int(sum(counts[:len(vis_rows)])), ntext=ntext, ntext_cap=ntext_cap,
                 vis_rows=vr.astype(np.int32), text_ids=np.asarray(text_ids, np.int32), text_rows=np.asarray(text_rows, np.int32))
 
 
@@ -132,6 +185,36 @@ def front_end_bucket_key(bank: int, front_cus: int, frames: int, height: int, wi
     return (bank, front_cus, frames, height, width, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
 
 
+class _PrefixHolders:
+    """`caption_stream(share_key=)`'s cache: key -> the KV sequence that holds the leading pages of the first clip of that key, its
+    kept visual rows and its splice plan.  Least recently used out.  Lives for one caption_stream call."""
+
+    def __init__(self, seqs: Sequence[int]):
+        from collections import OrderedDict
+        self.free = list(seqs)
+        self.entries = OrderedDict()
+        self.plans = {}                                  # (prompt, frames, rows per frame, fork) -> (device splice plan, device length)
+
+    def get(self, key):
+        e = self.entries.get(key)
+        if e is not None:
+            self.entries.move_to_end(key)
+        return e
+
+    def put(self, key, **entry) -> Optional[dict]:
+        """a holder sequence for `key`: a free one, or the least recently used entry's; None without capacity"""
+        if key in self.entries:
+            seq = self.entries.pop(key)["seq"]
+        elif self.free:
+            seq = self.free.pop()
+        elif self.entries:
+            seq = self.entries.popitem(last=False)[1]["seq"]
+        else:
+            return None
+        self.entries[key] = dict(entry, seq=seq)
+        return self.entries[key]
+
+
 @dataclass(frozen=True)
 class _BankState:
     """Host view of one generation bank: the batch and max_new of its last accepted begin_batch."""
@@ -142,10 +225,16 @@ class _BankState:
 class AuroraCapEngine:
     def __init__(self, cfg: dict, weights: dict, *, max_frames: int = 8, max_batch: int = 1, max_ctx: int = 4096,
                  max_new_tokens: int = 256, page_tokens: int = 64, use_graph: bool = True, num_banks: int = 1,
-                 max_image: Optional[int] = None, device: str = "cuda:0", spare_slots: int = 0, prompt_bucket: int = 0):
+                 max_image: Optional[int] = None, device: str = "cuda:0", spare_slots: int = 0, prompt_bucket: int = 0,
+                 prefix_cache: int = 0):
         # prompt_bucket: 0 = prompts are prefilled at their exact length (equal lengths share a pass, one captured front end per
         # length); 32 / 64 / 128 = at the next multiple of it, lengths in device memory (`prefill_groups`, `front_end_bucket_key`)
         self.prompt_bucket = check_prompt_bucket(prompt_bucket)
+        # prefix_cache: how many of the spare KV sequences (the last ones) `caption_stream(share_key=)` keeps as HOLDERS of a keyed
+        # clip's leading pages, for later clips of the same key to copy from; they are never a target of a commit's row exchange
+        if not 0 <= int(prefix_cache) <= max(int(spare_slots), 0):
+            raise ValueError(f"prefix_cache {prefix_cache} outside [0, spare_slots {spare_slots}]")
+        self.prefix_cache = int(prefix_cache)
         if not torch.cuda.is_available():
             raise _lib.AuroraHipError("AuroraCapEngine needs a ROCm GPU (torch.cuda.is_available() is False); "
                                       "there is no CPU fallback")
@@ -510,7 +599,7 @@ class AuroraCapEngine:
     def prefill(self, slot: int, embeds: torch.Tensor, seq_len: int):
         check(self.ctx, self.L.aur_llm_prefill(self.ctx, slot, embeds.data_ptr(), seq_len, self._stream()), "aur_llm_prefill")
 
-    def _lens_arg(self, seq_lens, nseq: int, stride: int) -> torch.Tensor:
+    def _lens_arg(self, seq_lens, nseq: int, stride: int, pos0: int = 0) -> torch.Tensor:
         """seq_lens of a variable-length prefill as the int32 device tensor the kernels read: a list is checked here (the only place
         the lengths are known on the host) and uploaded; a device tensor is the caller's promise and is passed through."""
         if torch.is_tensor(seq_lens):
@@ -519,7 +608,7 @@ class AuroraCapEngine:
             if stride < 32 or stride % 32:
                 raise ValueError(f"stride {stride} is not a positive multiple of 32")
             return seq_lens
-        lens = check_seq_lens(seq_lens, stride, self._max_new, self.c.max_ctx)
+        lens = check_seq_lens(seq_lens, stride, self._max_new, self.c.max_ctx, pos0)
         if len(lens) != nseq:
             raise ValueError(f"{len(lens)} lengths for {nseq} sequences")
         t = torch.tensor(lens, dtype=torch.int32, device=self.dev)
@@ -559,6 +648,38 @@ class AuroraCapEngine:
             return
         check(self.ctx, self.L.aur_llm_prefill_commit(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), seq_len, self._stream()),
               "aur_llm_prefill_commit")
+
+    # ------------------------------------------------------------------ shared prefixes
+    def kv_copy_prefix(self, src_seq: int, dst_seq0: int, ndst: int, tokens: int):
+        """K / V of positions [0, tokens) of KV sequence `src_seq` -> sequences [dst_seq0, dst_seq0 + ndst) of the current bank, every
+        layer, in one launch that reads the source once (enqueue-only; `tokens` a multiple of the 64-token page)."""
+        check(self.ctx, self.L.aur_kv_copy_prefix(self.ctx, src_seq, dst_seq0, ndst, tokens, self._stream()), "aur_kv_copy_prefix")
+
+    def extend_batch(self, slot0: int, nseq: int, embeds: torch.Tensor, pos0: int, stride: int, new_lens):
+        """`prefill_batch(seq_lens=)` for slots that already hold positions [0, pos0) (`kv_copy_prefix`, or an earlier prefill): embeds
+        [nseq * stride, d], rows [i * stride, i * stride + new_lens[i]) = positions [pos0, pos0 + new_lens[i]).  Bitwise what
+        `prefill(slot, full_embeds, pos0 + new_lens[i])` gives.  new_lens: a list (checked here) or an int32 device tensor."""
+        lens = self._lens_arg(new_lens, nseq, stride, pos0)
+        check(self.ctx, self.L.aur_llm_extend_batch_var(self.ctx, slot0, nseq, embeds.data_ptr(), pos0, stride, lens.data_ptr(), self._stream()),
+              "aur_llm_extend_batch_var")
+
+    def extend_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, pos0: int, stride: int, new_lens):
+        """The layer stack of `extend_batch` into KV sequences [seq0, seq0 + nseq): touches no decode state (see `prefill_stage`)."""
+        lens = self._lens_arg(new_lens, nseq, stride, pos0)
+        check(self.ctx, self.L.aur_llm_extend_stage_var(self.ctx, seq0, nseq, embeds.data_ptr(), pos0, stride, lens.data_ptr(), self._stream()),
+              "aur_llm_extend_stage_var")
+
+    def extend_commit(self, slot0: int, nseq: int, seq0: int, embeds: torch.Tensor, pos0: int, stride: int, new_lens):
+        """`prefill_commit` for sequences staged by `extend_stage` (same pos0, stride and lengths): decode position pos0 + new_lens[i]."""
+        lens = self._lens_arg(new_lens, nseq, stride, pos0)
+        check(self.ctx, self.L.aur_llm_extend_commit_var(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), pos0, stride, lens.data_ptr(),
+                                                         self._stream()), "aur_llm_extend_commit_var")
+
+    def _extend_rows(self, vis: torch.Tensor, plan: dict, fork: int, out: torch.Tensor):
+        """Rows [fork, seq_len) of a sibling prompt's spliced embeddings -> out[: seq_len - fork] (its own plan over the kept visual
+        rows: the projector runs, the ViT does not)."""
+        emb, L = self.project_splice(vis, plan=plan)
+        out[:L - fork].copy_(emb[fork:L])
 
     def decode(self, steps: int):
         check(self.ctx, self.L.aur_llm_decode(self.ctx, steps, self._stream()), "aur_llm_decode")
@@ -661,16 +782,24 @@ class AuroraCapEngine:
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
-                      streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+                      streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None) -> List[List[int]]:
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
         Every kernel on the path is batch-invariant, so each clip gets exactly the ids it gets when captioned alone.
-        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip i draws with stream streams[i] (default: i)."""
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip i draws with stream streams[i] (default: i).
+        share: one hashable key per clip, or None.  Clips with equal non-None keys are the same visual input (the caller's word:
+        several prompts about one video).  The first clip of a key is prefilled as always; each later one runs no ViT - its own plan
+        is spliced over the first clip's kept visual rows -, takes the whole KV pages the two prompts have in common from the first
+        clip's slot (`kv_copy_prefix`) and prefills only its remaining rows, neighbouring siblings in one pass (`extend_batch`).  A
+        sibling whose prompt shares less than a page with the first clip's, or diverges from it before the visual rows end, takes the
+        unshared path.  The same ids either way; share=None is exactly the path above."""
         B = len(clips)
         samp = S.check_sampling(sampling)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{B} clips for an engine built with max_batch={self.max_batch}")
+        if share is not None and len(share) != B:
+            raise ValueError(f"{len(share)} share keys for {B} clips")
         d = self.l["hidden_size"]
         rs, plans = [], []
         for px, ids in clips:
@@ -678,20 +807,59 @@ class AuroraCapEngine:
             t0 = (px.shape[-2] // self.v["patch_size"]) * (px.shape[-1] // self.v["patch_size"]) + 1     # as vit_encode counts them
             rs.append(r)
             plans.append(self.splice_plan(ids, px.shape[0], tokens_at_layer(t0, r, self.v["num_hidden_layers"] - 1) - 1))
+        # siblings: clip -> (first clip of its key, fork position); everything else is a run of clips prefilled as always
+        child, first = {}, {}
+        for i, key in enumerate(share if share is not None else ()):
+            if key is None:
+                continue
+            p = first.setdefault(key, i)
+            if p != i and clips[p][0].shape == clips[i][0].shape:
+                fork = share_fork(plans[p], plans[i])
+                if fork > 0:
+                    child[i] = (p, fork)
+        keep_vis = {p for p, _ in child.values()}
+        vis_of = {}
         if samp is not None:
             self._sampling_on()
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
-        for b, g, stride in prefill_groups([p["seq_len"] for p in plans], prefill_group, self.prompt_bucket):
-            lens = [plans[b + i]["seq_len"] for i in range(g)]
-            mixed = len(set(lens)) > 1                            # only with a bucket: lengths go to the device, rows beyond them are don't-care
-            L = stride if mixed else lens[0]
-            Lp = _rup(L, 32)
-            buf = torch.empty(g * Lp, d, dtype=torch.float16, device=self.dev)
-            for i in range(g):
-                vis = self.vit_encode(clips[b + i][0], rs[b + i])
-                self.project_splice(vis, out=buf[i * Lp:(i + 1) * Lp], plan=plans[b + i])
-            self.prefill_batch(b, g, buf, L, seq_lens=lens if mixed else None)
+        runs, b0 = [], 0                                          # maximal runs of neighbouring clips that are nobody's sibling
+        for i in range(B + 1):
+            if i == B or i in child:
+                if i > b0:
+                    runs.append((b0, i))
+                b0 = i + 1
+        for r0, r1 in runs:
+            for b, g, stride in prefill_groups([p["seq_len"] for p in plans[r0:r1]], prefill_group, self.prompt_bucket):
+                b += r0
+                lens = [plans[b + i]["seq_len"] for i in range(g)]
+                mixed = len(set(lens)) > 1                        # only with a bucket: lengths go to the device, rows beyond them are don't-care
+                L = stride if mixed else lens[0]
+                Lp = _rup(L, 32)
+                buf = torch.empty(g * Lp, d, dtype=torch.float16, device=self.dev)
+                for i in range(g):
+                    vis = self.vit_encode(clips[b + i][0], rs[b + i])
+                    if b + i in keep_vis:
+                        vis_of[b + i] = vis
+                    self.project_splice(vis, out=buf[i * Lp:(i + 1) * Lp], plan=plans[b + i])
+                self.prefill_batch(b, g, buf, L, seq_lens=lens if mixed else None)
+        i = 0
+        while i < B:                                              # neighbouring siblings of one (first clip, fork): one copy, one pass
+            if i not in child:
+                i += 1
+                continue
+            g = 1
+            while i + g in child and child[i + g] == child[i] and g < prefill_group:
+                g += 1
+            p, fork = child[i]
+            new = [plans[i + j]["seq_len"] - fork for j in range(g)]
+            stride = _rup(max(new), 32)
+            buf = torch.empty(g * stride, d, dtype=torch.float16, device=self.dev)
+            for j in range(g):
+                self._extend_rows(vis_of[p], plans[i + j], fork, buf[j * stride:(j + 1) * stride])
+            self.kv_copy_prefix(p, i, g, fork)
+            self.extend_batch(i, g, buf, fork, stride, new)
+            i += g
         done = 1
         while done < max_new_tokens:
             n = min(check_every, max_new_tokens - done) if eos_id is not None else max_new_tokens - done
@@ -700,6 +868,19 @@ class AuroraCapEngine:
             if eos_id is not None and self.unfinished() == 0:
                 break
         return self.outputs()
+
+    def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
+                        eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
+        (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives."""
+        prompts = [list(ids) for ids in list_of_input_ids]
+        st = list(range(len(prompts))) if streams is None else [int(x) for x in streams]
+        out: List[List[int]] = []
+        for c0 in range(0, len(prompts), self.max_batch):
+            chunk = prompts[c0:c0 + self.max_batch]
+            out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
+                                      streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk))
+        return out
 
     # ------------------------------------------------------------------ continuous batching
     def slot_reset(self, slot: int):
@@ -724,7 +905,7 @@ class AuroraCapEngine:
 
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
-                       sampling: Optional[dict] = None, stream_of=None):
+                       sampling: Optional[dict] = None, stream_of=None, share_key=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -740,20 +921,31 @@ class AuroraCapEngine:
         bucket on first use (`_front_end_replay`); False = ~600 eager launches per clip.  Same ids either way.
         sampling=dict(temperature, top_k, top_p, seed): sampled captions; a clip's stream is its index in `clips` (or
         stream_of(index), called when the clip is about to get its slot), whatever slot it lands in and whenever (a re-filled slot
-        gets the new clip's record before its first token is picked)."""
+        gets the new clip's record before its first token is picked).
+        share_key: callable index -> hashable key | None (an engine built with prefix_cache >= 1).  Clips of equal key are the same
+        visual input.  A keyed clip that misses the cache runs its normal front end, after which its leading whole pages are copied
+        into a holder sequence (kept visual rows and plan beside it); one that hits runs no ViT: copy from the holder, its own plan
+        spliced over the kept visual rows, and a prefill of the rows behind the fork only (`share_fork`; a clip that cannot fork takes
+        the normal path).  In the overlapped mode such a front end runs eagerly on the front-end stream (never from a captured graph).
+        Same ids either way.  An engine whose only spare sequences are holders must be called with overlap=False: the default
+        follows spare_slots."""
         samp = S.check_sampling(sampling)
         if samp is not None:
             self._sampling_on()
         B = self.max_batch if slots is None else slots
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"slots={B} for an engine built with max_batch={self.max_batch}")
+        if share_key is not None and self.prefix_cache < 1:
+            raise ValueError("caption_stream(share_key=) needs an engine built with prefix_cache >= 1")
         if overlap is None:
             overlap = self.spare_slots > 0
+        n_hold = self.prefix_cache if share_key is not None else 0
+        holders = _PrefixHolders(range(self.max_batch + self.spare_slots - n_hold, self.max_batch + self.spare_slots)) if n_hold else None
         if overlap:
-            if self.spare_slots < 1:
-                raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1")
+            if self.spare_slots - n_hold < 1:
+                raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1 beyond its prefix_cache")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph, samp, stream_of)
+                                                       front_graph, samp, stream_of, share_key, holders)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -771,12 +963,26 @@ class AuroraCapEngine:
                     idx, (px, ids) = nxt
                     try:
                         r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
+                        key = share_key(idx) if share_key is not None else None
+                        hit = self._holder_hit(holders, key, px, list(ids), r) if key is not None else None
+                        if hit is not None:                       # a sibling: pages from the holder, then the rows behind the fork
+                            h, fork, buf, stride, new = hit
+                            self.kv_copy_prefix(h["seq"], s, 1, fork)
+                            self.slot_reset(s)
+                            if samp is not None:
+                                self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
+                            self.extend_batch(s, 1, buf, fork, stride, new)
+                            owner[s] = idx
+                            continue
                         vis = self.vit_encode(px, r)
-                        emb, L = self.project_splice(vis, list(ids))
+                        plan = self.splice_plan(list(ids), vis.shape[0], vis.shape[1]) if key is not None else None
+                        emb, L = self.project_splice(vis, list(ids), plan=plan)
                         self.slot_reset(s)
                         if samp is not None:
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                         self.prefill(s, emb, L)                   # argument checks come before any enqueue: a rejection leaves the slot idle
+                        if key is not None:
+                            self._holder_fill(holders, key, s, vis, plan, px, r)
                         owner[s] = idx
                     except (ValueError, IndexError, AssertionError, _lib.AuroraHipError) as e:
                         if on_error is None:
@@ -792,6 +998,42 @@ class AuroraCapEngine:
                 for s in done:
                     yield owner[s], out[s]
                     owner[s] = None
+
+    def _holder_hit(self, holders: "_PrefixHolders", key, px: torch.Tensor, ids: List[int], r: int):
+        """A keyed clip against the holder cache: None (miss, another input shape, or a prompt that cannot fork) or (entry, fork, the
+        rows [fork, seq_len) of its spliced prompt in a buffer of `stride` rows, stride, their number as the device tensor the extend
+        calls read).  Everything the host can reject is rejected here, before anything touches a KV sequence."""
+        e = holders.get(key)
+        if e is None or e["shape"] != tuple(px.shape) or e["r"] != r:
+            return None
+        vis = e["vis"]
+        host = splice_rows(ids, vis.shape[0], vis.shape[1])       # the decision needs no device: a prompt that cannot fork costs no upload
+        fork = min(share_fork(e["plan"], host), e["tokens"])
+        if fork <= 0:
+            return None
+        new = host["seq_len"] - fork
+        stride = _rup(new, 32)
+        check_seq_lens([new], stride, self._max_new, self.c.max_ctx, fork)
+        # the device arrays of a prompt (three row maps and the length: blocking uploads) are built once per distinct prompt of the
+        # call - a benchmark asks the same few questions about every video - and reused by every later hit
+        pk = (tuple(ids), vis.shape[0], vis.shape[1], fork)
+        if pk not in holders.plans:
+            holders.plans[pk] = (self.splice_plan(ids, vis.shape[0], vis.shape[1]), torch.tensor([new], dtype=torch.int32, device=self.dev))
+        plan, new_dev = holders.plans[pk]
+        buf = torch.empty(stride, self.l["hidden_size"], dtype=torch.float16, device=self.dev)
+        self._extend_rows(vis, plan, fork, buf)
+        return e, fork, buf, stride, new_dev
+
+    def _holder_fill(self, holders: "_PrefixHolders", key, seq: int, vis: torch.Tensor, plan: dict, px: torch.Tensor, r: int):
+        """After the front end of a keyed clip that missed, on the stream that ran it: its leading whole pages go from KV sequence
+        `seq` into a holder, its kept visual rows and plan are kept beside it.  A key that already has a holder keeps it (the clip
+        could not fork from it: its prompt differs early), and so does a prompt shorter than a page."""
+        tokens = fork_point(plan["seq_len"])
+        if tokens <= 0 or plan["nvis"] < 1 or holders.get(key) is not None:
+            return
+        e = holders.put(key, vis=vis, plan=plan, shape=tuple(px.shape), r=r, tokens=tokens)
+        if e is not None:
+            self.kv_copy_prefix(seq, e["seq"], 1, tokens)
 
     def _masked_streams(self, front_cus: int):
         """(front-end stream on `front_cus` CUs of every XCD, decode stream on the other CUs); shared per process (streams.py)."""
@@ -810,7 +1052,8 @@ class AuroraCapEngine:
         recently used evicted): the per-bucket capture of the reference tree's serving engine
         (src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279).  Returns (embeds, seq_len) for `prefill_commit`
         - with `prompt_bucket`, (embeds, (stride, lengths buffer)): the bucket no longer depends on the exact prompt length -;
-        `embeds` is the bucket's static buffer: the caller orders the next replay of the same bucket (same `seq`) after that commit."""
+        `embeds` is the bucket's static buffer: the caller orders the next replay of the same bucket (same `seq`) after that commit.
+        Third value: the graph that ran (its `vis` holds the clip's kept visual rows until the bucket's next replay)."""
         if px.dim() != 4 or px.shape[1] != self.v.get("num_channels", 3):
             raise ValueError(f"pixel_values must be [frames, {self.v.get('num_channels', 3)}, H, W], got {tuple(px.shape)}")
         F, H, W = int(px.shape[0]), int(px.shape[-2]), int(px.shape[-1])
@@ -846,10 +1089,10 @@ class AuroraCapEngine:
         fg.launch()
         fg._last = torch.cuda.Event()
         fg._last.record(torch.cuda.current_stream(self.dev))
-        return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"])
+        return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"]), fg
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
-                                   samp=None, stream_of=None):
+                                   samp=None, stream_of=None, share_key=None, holders=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -858,7 +1101,8 @@ class AuroraCapEngine:
             self.slot_retire(s)
         it = iter(enumerate(clips))
         owner: List[Optional[int]] = [None] * B
-        free_seqs = list(range(self.max_batch, self.max_batch + self.spare_slots))     # spare KV sequences holding no prepared clip
+        n_hold = len(holders.free) if holders is not None else 0                       # the last spare sequences hold shared prefixes
+        free_seqs = list(range(self.max_batch, self.max_batch + self.spare_slots - n_hold))     # spare KV sequences holding no prepared clip
         reusable = {}                                             # sequence -> event after which its (exchanged) pages may be rewritten
         staged = deque()                                          # prepared clips: (index, sequence, embeds, L, event)
         exhausted = False
@@ -875,7 +1119,10 @@ class AuroraCapEngine:
                         emb.record_stream(sD)
                         if samp is not None:                      # the captured front end holds the stage only: the pick is the commit's
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
-                        if isinstance(L, tuple):                  # a bucketed front end: (stride, the graph's static lengths buffer)
+                        if isinstance(L, tuple) and L[0] == "extend":     # a sibling staged behind a copied prefix: (_, fork, stride, rows)
+                            L[3].record_stream(sD)
+                            self.extend_commit(s, 1, seq, emb, L[1], L[2], L[3])
+                        elif isinstance(L, tuple):                # a bucketed front end: (stride, the graph's static lengths buffer)
                             self.prefill_commit(s, 1, seq, emb, L[0], seq_lens=L[1])
                         else:
                             self.prefill_commit(s, 1, seq, emb, L)
@@ -921,12 +1168,27 @@ class AuroraCapEngine:
                             if seq in reusable:
                                 sF.wait_event(reusable.pop(seq))
                             r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
-                            if front_graph:
-                                emb, L = self._front_end_replay(px, list(ids), r, seq, front_cus)      # one hipGraph replay per clip (captured per bucket)
+                            key = share_key(idx) if share_key is not None else None
+                            hit = self._holder_hit(holders, key, px, list(ids), r) if key is not None else None
+                            if hit is not None:                   # a sibling: no ViT, eager on this stream into its spare sequence
+                                h, fork, emb, stride, new = hit
+                                self.kv_copy_prefix(h["seq"], seq, 1, fork)
+                                self.extend_stage(seq, 1, emb, fork, stride, new)
+                                L = ("extend", fork, stride, new)
+                            elif front_graph:
+                                emb, L, fg = self._front_end_replay(px, list(ids), r, seq, front_cus)  # one hipGraph replay per clip (captured per bucket)
+                                if key is not None:
+                                    # the graph's visual rows are a static buffer: the holder keeps a copy.  Its plan is the host form
+                                    # (`splice_rows`): a holder's plan is only ever compared (`share_fork`), a sibling is spliced with its own
+                                    self._holder_fill(holders, key, seq, fg.vis[:px.shape[0]].clone(), splice_rows(list(ids), px.shape[0], fg.n_kept),
+                                                      px, r)
                             else:
                                 vis = self.vit_encode(px, r)
-                                emb, L = self.project_splice(vis, list(ids))
+                                plan = self.splice_plan(list(ids), vis.shape[0], vis.shape[1]) if key is not None else None
+                                emb, L = self.project_splice(vis, list(ids), plan=plan)
                                 self.prefill_stage(seq, 1, emb, L)    # argument checks come before any enqueue
+                                if key is not None:               # before the event the commit waits on: the exchange comes later
+                                    self._holder_fill(holders, key, seq, vis, plan, px, r)
                             ev = torch.cuda.Event()
                             ev.record(sF)
                         staged.append((idx, seq, emb, L, ev))

@@ -128,11 +128,13 @@ class AuroraModel:
         model.llm.generation_top_k = generation_top_k(path)
         return model
 
-    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None):
+    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
-        sampling=dict(temperature, top_k, top_p, seed): sampled captions, clip i drawing with stream streams[i] (default: i)."""
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions, clip i drawing with stream streams[i] (default: i).
+        share: one hashable key per clip (or None); clips of equal key are the same visual input and share its ViT pass and the KV
+        of their common prefix inside a chunk of max_batch clips (AuroraCapEngine.caption_batch)."""
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
@@ -141,21 +143,44 @@ class AuroraModel:
             group = [(px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips[c0:c0 + B]]
             st = range(c0, c0 + len(group)) if streams is None else list(streams)[c0:c0 + len(group)]
             kw = dict(sampling=sampling, streams=st) if sampling is not None else {}
+            if share is not None:
+                kw["share"] = list(share)[c0:c0 + len(group)]
             out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 
+    def caption_prompts(self, pixel_values, list_of_input_ids, max_new_tokens: int = 2048, eos_token_id="default", sampling=None,
+                        streams=None):
+        """One clip, several prompts (the five VDC questions about a video): pixel_values [f, c, h, w], each prompt's input ids with
+        -200 markers -> one new-token id list per prompt, in order, each identical to captioning (clip, prompt) alone.  The ViT runs
+        once per chunk of max_batch prompts and the later prompts prefill only the rows behind the last visual token.  A slow-fast
+        model never shares: its prompts run one at a time through the three calls."""
+        prompts = [ids.tolist() if torch.is_tensor(ids) else list(ids) for ids in list_of_input_ids]
+        if self.slowfast:
+            out, ratio = [], self.visual_encoder.visual_token_merge_ratio
+            for k, ids in enumerate(prompts):
+                self.visual_encoder.reset_tome_r(ratio)                           # the slow-fast forward leaves it at 1.0
+                emb = self.forward({"pixel_values": pixel_values.unsqueeze(0), "input_ids": [ids]}, mode="inference")
+                kw = dict(do_sample=False) if sampling is None else dict(sampling, do_sample=True, stream=k if streams is None else list(streams)[k])
+                out.append(self.llm.generate(**emb, num_beams=1, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, **kw)[0].tolist())
+            self.visual_encoder.reset_tome_r(ratio)
+            return out
+        return self.caption_batch([(pixel_values, ids) for ids in prompts], max_new_tokens, eos_token_id, sampling, streams,
+                                  share=[0] * len(prompts))
+
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
-                       overlap=None, sampling=None, stream_of=None):
+                       overlap=None, sampling=None, stream_of=None, share_key=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): yields (index, new-token ids) as captions
         finish (EOS or max_new_tokens), re-filling freed KV slots with the next clips.  Per-clip results equal the
         one-at-a-time calls.  overlap (default: on for an engine with spare KV sequences): the next clips' front ends run
         ahead on a CU-masked stream while the slots decode (AuroraCapEngine.caption_stream).
-        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip k draws with stream stream_of(k) (default: k)."""
+        sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip k draws with stream stream_of(k) (default: k).
+        share_key: callable index -> key | None; clips of equal key are the same visual input (engine built with prefix_cache >= 1)."""
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         n = min(max_new_tokens, self.engine.max_new_tokens)
         it = ((px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips)
         yield from self.engine.caption_stream(it, self.visual_encoder.visual_token_merge_ratio, n, eos, check_every=check_every,
                                               on_error=on_error, overlap=overlap,
+                                              **(dict(share_key=share_key) if share_key is not None else {}),
                                               **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}))
 
     def __call__(self, data: dict, data_samples=None, mode: str = "loss"):

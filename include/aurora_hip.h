@@ -181,6 +181,34 @@ int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t se
 int aur_llm_prefill_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
 int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
 int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride, const int32_t* seq_lens_dev, void* stream);
+/* Shared prefixes: several prompts about one clip agree on every row up to and including the last visual token, so
+ * a sibling request takes those positions from the first request's KV sequence and prefills only the rows that differ.
+ *
+ * aur_kv_copy_prefix copies the K and V of positions [0, tokens) of KV sequence src_seq into sequences [dst_seq0, dst_seq0 + ndst) of
+ * the selected bank, for every layer (kv_copy_prefix_kernel: each 16-byte piece of a source page is loaded once and stored ndst times).
+ * The page ids are read from the page table ON THE DEVICE when the work runs: the call is enqueue-only, recordable with aur_graph_begin,
+ * and correct behind earlier aur_llm_prefill_commit row exchanges queued on the same stream.  tokens: a positive multiple of page_tokens
+ * (64), at most the positions of a sequence's pages; every id below max_batch + spare_slots; src_seq outside the destination range;
+ * anything else returns AUR_ERR_ARG and leaves the ctx usable.  Pages are COPIED, not shared: the static page table, the commit's row
+ * exchange and every decode kernel stay as they are - no reference counts, no copy-on-write.  The source may be a live, decoding slot
+ * (its pages below `tokens` are only read by its own decode steps).
+ *
+ * aur_llm_extend_*_var: the _prefill_*_var calls for sequences that already hold valid K / V for positions [0, pos0).  embeds is fp16
+ * [nseq * stride, llm_hidden]; its rows [i * stride, i * stride + len_i) are the input embeddings of positions [pos0, pos0 + len_i),
+ * len_i = new_lens_dev[i] (int32, device memory, clamped into [1, stride] by every kernel).  pos0: a positive multiple of page_tokens;
+ * stride: a multiple of 32; pos0 + stride at most the positions of a sequence's pages - anything else AUR_ERR_ARG.  pos0 + len_i +
+ * max_new_tokens <= max_ctx is the CALLER'S promise (aurora_amd.engine checks it where the lengths are known).  Inside it is the layer
+ * stack of the prefill over the new rows alone: RoPE and the page write at pos0 + row, queries at pos0 + row over keys [0, pos0 + len_i),
+ * padding rows cleared and kept zero, the pruned last layer (when the stride is long enough to prune) with its row0 relative to the new
+ * rows, the first token from row len_i - 1 - greedy, or sampled with the slot's record at token index 0 -, decode position pos0 + len_i.
+ * CONTRACT: for sequence i the first token, the logits row, every K / V value at positions [pos0, pos0 + len_i) and the decode position
+ * are BITWISE those of aur_llm_prefill(slot, full_embeds_i, pos0 + len_i), provided positions [0, pos0) hold what that prefill writes (a
+ * GEMM element's k order does not depend on M; attention is row-independent and walks the key blocks in order).  Recordable like their
+ * _prefill_ counterparts; a capture freezes pos0, stride, nseq, the ids and the pointers, not the lengths. */
+int aur_kv_copy_prefix(aur_ctx* ctx, int32_t src_seq, int32_t dst_seq0, int32_t ndst, int32_t tokens, void* stream);
+int aur_llm_extend_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride, const int32_t* new_lens_dev, void* stream);
+int aur_llm_extend_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride, const int32_t* new_lens_dev, void* stream);
+int aur_llm_extend_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t pos0, int32_t stride, const int32_t* new_lens_dev, void* stream);
 /* Sampled generation: with option "sampling" = 1 (aur_set_option) the token pick of every prefill / commit /
  * decode step draws from the slot's temperature / top-k / top-p distribution instead of taking the first maximum.  The draw for
  * (seed, stream, token index) is word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (token index, stream, 0, 0): a pure
@@ -214,7 +242,8 @@ int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_d
 /* ---- captured front ends (the reference tree's serving engine captures one graph per shape bucket and copies the inputs into the
  * graph's static buffers before every replay: src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279) ------------
  * aur_graph_begin opens a hipGraph capture on `stream` (thread-local mode); every enqueue-only call of this ctx that follows on that
- * stream from the same thread - aur_vit_encode(_hw), aur_project_splice(_var), aur_llm_prefill / _batch / _stage / _commit (and their _var forms), aur_slot_reset /
+ * stream from the same thread - aur_vit_encode(_hw), aur_project_splice(_var), aur_llm_prefill / _batch / _stage / _commit (and their _var forms),
+ * aur_kv_copy_prefix, aur_llm_extend_*_var, aur_slot_reset /
  * _retire / _collect, the kernel-level entry points - is recorded instead of run; aur_graph_end instantiates the recording and returns
  * a handle (>= 1) that aur_graph_launch replays with one call.  Pointers, shapes, KV sequence ids, the ctx's gemm_* knobs and the
  * current bank (whose page table the prefill writes through) are frozen at capture time: a serving loop keeps one graph per (bank,

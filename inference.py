@@ -40,6 +40,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--do_sample', action='store_true', help='seeded sampling with --temperature (required, > 0) / --top_p / --top_k instead of greedy decoding')
     parser.add_argument('--top_k', type=int, default=50, help='with --do_sample: keep the k most likely tokens (0 = off)')
     parser.add_argument('--seed', type=int, default=0, help='with --do_sample: seed of the counter-based generator (same seed, same caption)')
+    # more questions about the same input: the vision tower runs once and the later prompts prefill only the rows behind the last visual token
+    parser.add_argument('--extra_prompt', action='append', default=[], metavar='TEXT',
+                        help='a further instruction about the same visual input (repeatable): one more caption is printed per flag, in order; '
+                             'with --synthetic there is no tokenizer: the text is ignored and each flag adds a seeded prompt of its own length')
     return parser
 
 
@@ -57,11 +61,17 @@ def main():
         from aurora_amd.engine import AuroraCapEngine
         cfg = S.AURORACAP_7B
         w = {"vit": S.vit_weights(cfg["vit"]), "projector": S.projector_weights(1280, 4096), "llm": S.llm_weights(cfg["llm"])}
-        eng = AuroraCapEngine(cfg, w, max_frames=args.num_frm, max_batch=1, max_ctx=30 + args.num_frm * 729 + args.max_new_tokens + 64,
+        n_prompts = 1 + len(args.extra_prompt)
+        eng = AuroraCapEngine(cfg, w, max_frames=args.num_frm, max_batch=n_prompts,
+                              max_ctx=30 + args.num_frm * 729 + args.max_new_tokens + 64 + 3 * len(args.extra_prompt),
                               max_new_tokens=args.max_new_tokens)
         model = AuroraModel(eng, eos_token_id=None)
         data = {"pixel_values": S.frames(args.num_frm, 0).unsqueeze(0), "input_ids": torch.tensor([S.prompt_ids(args.num_frm, 0)])}
         tokenizer = None
+        # the j-th extra prompt: the same ids up to the last image marker, then a seeded tail of its own length
+        ids0 = S.prompt_ids(args.num_frm, 0)
+        head = ids0[:len(ids0) - ids0[::-1].index(-200)]
+        extra_ids = [head + np.random.default_rng(3000 + j).integers(3, 32000, size=8 + 3 * j).tolist() for j in range(len(args.extra_prompt))]
     else:
         from transformers import AutoTokenizer, CLIPImageProcessor
         if not osp.isdir(args.model_path):
@@ -100,15 +110,23 @@ def main():
         else:
             sys.exit("error: --visual_input must end with mp4, png or jpg")
         data["input_ids"] = process_text(build_prompt(args.prompt, n_img), tokenizer)
+        extra_ids = [process_text(build_prompt(p, n_img), tokenizer)[0].tolist() for p in args.extra_prompt]
         # The engine's capacity comes from THIS request: read_video_pyav may return num_frm + 1 frames and the
         # prompt length is only known after tokenising, so size the context from the spliced length, not from the flags.
-        n_text = int((data["input_ids"] != -200).sum())
+        n_text = max(sum(1 for t in ids if t != -200) for ids in [data["input_ids"][0].tolist()] + extra_ids)
         per_frame = (image_size // patch) ** 2                                      # upper bound: token_kept_ratio = 1.0 keeps all patches
         max_ctx = -(-(n_text + n_img * per_frame + args.max_new_tokens) // 64) * 64
         model = AuroraModel.from_pretrained(args.model_path, max_frames=max(n_img, 1), max_ctx=max_ctx,
-                                            max_new_tokens=args.max_new_tokens)
+                                            max_new_tokens=args.max_new_tokens, max_batch=1 + len(extra_ids))
 
     model.visual_encoder.reset_tome_r(args.token_kept_ratio)
+    if extra_ids:                     # several prompts about one input: one caption per prompt, in order
+        px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
+        samp = dict(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=args.seed) if args.do_sample else None
+        outs = model.caption_prompts(px, [data["input_ids"][0].tolist()] + extra_ids, max_new_tokens=args.max_new_tokens, sampling=samp)
+        for ids in outs:
+            print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
+        return
     output = model(data, mode="inference")
     sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
     cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
