@@ -1115,8 +1115,9 @@ static int var_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds,
 // lens != nullptr: seq_len is the stride (checked by var_args) and the rows [lens[i], stride) of every sequence are cleared first: whatever
 // the caller left there, they are zeros in every layer (an all-zero row stays zero through norm, projections, RoPE and the MLP, and the
 // attention kernel stores zeros for it), and so are the K / V written for them.
+// prune = false (aur_llm_score_var): the last layer runs over every row like the others - rows in front of the last 128 are read after it.
 static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who, const int32_t* lens = nullptr,
-                          int pos0 = 0) {
+                          int pos0 = 0, bool prune_ok = true) {
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
@@ -1128,7 +1129,7 @@ static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int se
     if (lens) CK(launch_clear_tail_rows((half_t*)embeds, g.llm_hidden, nseq, Mseq, lens, s));
     for (int l = 0; l < g.llm_layers; ++l) {
         // the compact scratch of the pruned last layer must fit l_h: nseq * 128 * (3 d + mlp) <= nseq * Mseq * mlp (and LB < Mseq)
-        const bool prune = ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
+        const bool prune = prune_ok && ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
         int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0)
                        : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0);
         if (rc) return rc;
@@ -1273,6 +1274,64 @@ extern "C" int aur_llm_extend_commit_var(aur_ctx* ctx, int32_t slot0, int32_t ns
     if (!new_lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_commit_var: null new_lens_dev");
     if (int rc = extend_pos_args(ctx, "aur_llm_extend_commit_var", pos0, stride)) return rc;      // stride / nseq / embeds: var_args, in prefill_commit
     return prefill_commit(ctx, slot0, nseq, seq0, embeds, stride, stream, new_lens_dev, pos0);
+}
+
+// ---- scoring given continuations: the layer stack of a _stage_var pass, then ANY of its rows through the pick path's lm_head and
+// score_rows_kernel.  Scratch (the caller's; a function of cfg alone): x fragments of round_up(max_batch, 16) columns | sum(x^2) stripes |
+// fp32 logits [max_batch, vocab] | int32 effective targets [max_batch], each region 256-byte aligned.
+static int64_t score_xf_bytes(const aur_ctx* c) { return rup64((int64_t)rup(c->cfg.max_batch, 16) * c->cfg.llm_hidden * 2, 256); }
+static int64_t score_ssq_bytes() { return (int64_t)AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8; }
+static int64_t score_logits_bytes(const aur_ctx* c) { return rup64((int64_t)c->cfg.max_batch * c->cfg.llm_vocab * 4, 256); }
+extern "C" int64_t aur_score_scratch_bytes(const aur_ctx* ctx) {
+    return score_xf_bytes(ctx) + score_ssq_bytes() + score_logits_bytes(ctx) + rup64((int64_t)ctx->cfg.max_batch * 4, 256);
+}
+
+extern "C" int aur_llm_score_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride, const int32_t* lens_dev,
+                                 const int32_t* score_rows_dev, const int32_t* score_targets_dev, int32_t nscore_cap, void* scratch,
+                                 int64_t scratch_bytes, float* logprob_out, int32_t* argmax_out, float* logits_out, void* stream) {
+    const char* who = "aur_llm_score_var";
+    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", who, seq0, seq0 + nseq, ctx->kv_seqs);
+    if (int rc = var_args(ctx, who, nseq, embeds, stride, lens_dev)) return rc;
+    if (pos0 != 0)
+        if (int rc = extend_pos_args(ctx, who, pos0, stride)) return rc;
+    if (!score_rows_dev || !score_targets_dev || !logprob_out || !argmax_out || nscore_cap < 1)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: null entry / output array or nscore_cap %d < 1", who, nscore_cap);
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < aur_score_scratch_bytes(ctx))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: scratch must be 256-byte aligned and hold aur_score_scratch_bytes = %lld bytes (got %lld)", who,
+                        (long long)aur_score_scratch_bytes(ctx), (long long)scratch_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, s, who, lens_dev, pos0, false)) return rc;
+    stage_end(ctx, "prefill", s);
+    const aur_config& g = ctx->cfg;
+    const int B = g.max_batch;
+    half_t* xf = (half_t*)scratch;
+    unsigned long long* ssq = (unsigned long long*)((char*)scratch + score_xf_bytes(ctx));
+    float* lg = (float*)((char*)ssq + score_ssq_bytes());
+    int32_t* tgt = (int32_t*)((char*)lg + score_logits_bytes(ctx));
+    stage_begin(ctx, "score", s);
+    for (int j0 = 0; j0 < nscore_cap; j0 += B) {
+        const int n = nscore_cap - j0 < B ? nscore_cap - j0 : B;
+        CK(launch_score_gather((const half_t*)embeds, g.llm_hidden, score_rows_dev + j0, score_targets_dev + j0, n, B, nseq, stride, lens_dev, xf,
+                               ssq, tgt, s));
+        SkinnyArgs h{};       // as lm_head_and_advance sets it up, on the caller's scratch and at the engine's capacity
+        h.xf = xf; h.W = ctx->l_head_w; h.B = B; h.Npad = ctx->l_vocab_pad; h.K = g.llm_hidden; h.n_real = g.llm_vocab;
+        h.mode = SK_LOGITS; h.out32 = lg; h.b_lo = 0; h.b_hi = n; h.ssq_in = ssq; h.norm_eps = g.llm_rms_eps;
+        h.variant = ctx->skinny_variant;
+        CK(launch_skinny(h, s));
+        CK(launch_score_rows(lg, n, g.llm_vocab, tgt, logprob_out + j0, argmax_out + j0, s));
+        if (logits_out) CK(hipMemcpyAsync(logits_out + (int64_t)j0 * g.llm_vocab, lg, (size_t)n * g.llm_vocab * 4, hipMemcpyDeviceToDevice, s));
+    }
+    stage_end(ctx, "score", s);
+    return AUR_OK;
+}
+
+extern "C" int aur_score_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* targets_dev, float* logprob_out,
+                              int32_t* argmax_out, void* stream) {
+    if (!ctx || !logits || !targets_dev || !logprob_out || !argmax_out) return aur_fail(ctx, AUR_ERR_ARG, "aur_score_rows: null argument");
+    if (rows < 1 || vocab < 1) return aur_fail(ctx, AUR_ERR_ARG, "aur_score_rows: rows %d or vocab %d < 1", rows, vocab);
+    CK(launch_score_rows(logits, rows, vocab, targets_dev, logprob_out, argmax_out, (hipStream_t)stream));
+    return AUR_OK;
 }
 
 // K and V of positions [0, tokens) of KV sequence src_seq -> sequences [dst_seq0, dst_seq0 + ndst) of the selected bank, every layer.

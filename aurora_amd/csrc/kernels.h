@@ -215,3 +215,13 @@ hipError_t launch_sample_advance(const float* logits, int b0, int nb, int vocab,
                                  int len_cap, int stage);
 hipError_t launch_sample_rows(const float* logits, int rows, int vocab, const aur_sampling* params, const int32_t* n_dev,
                               int32_t* tokens_out, int32_t* kept_out, hipStream_t s, int stage);
+
+// ---- score.hip: log-probability of a target token under a logits row (+ the row's first argmax), and the row-list gather that feeds
+// any rows of a prefill pass to the pick path's lm_head (aur_llm_score_var)
+hipError_t launch_score_rows(const float* logits, int rows, int vocab, const int32_t* targets, float* logprob_out, int32_t* argmax_out,
+                             hipStream_t s);
+// column b < n of xf = flat row rows[b] of x (sequence rows[b] / stride, row rows[b] % stride) + its sum(x^2); entries that are negative,
+// outside nseq * stride or at / beyond their sequence's clamped length - and columns [n, ncols) - are zero rows; eff_targets[b] =
+// targets[b] for a live entry, -1 otherwise
+hipError_t launch_score_gather(const half_t* x, int d, const int32_t* rows, const int32_t* targets, int n, int ncols, int nseq, int stride,
+                               const int32_t* lens, half_t* xf, unsigned long long* ssq_out, int32_t* eff_targets, hipStream_t s);

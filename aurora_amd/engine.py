@@ -185,6 +185,51 @@ def front_end_bucket_key(bank: int, front_cus: int, frames: int, height: int, wi
     return (bank, front_cus, frames, height, width, r, seq, plan["seq_len"], plan["used"], plan["nvis"], plan["ntext"])
 
 
+# ---- scoring given continuations (`AuroraCapEngine.loglikelihood_batch`): the host-side layout, no device
+def loglik_ids(context_ids: Sequence[int], continuation_ids: Sequence[int]) -> List[int]:
+    """The prompt a continuation is scored from: context + continuation[:-1] - the last continuation token is only ever a target
+    (`aurora_amd.scoring`).  The context may hold image markers (-200); a continuation is plain token ids."""
+    cont = [int(t) for t in continuation_ids]
+    if any(t < 0 for t in cont):
+        raise ValueError("a continuation holds token ids only (no image marker)")
+    return [int(t) for t in context_ids] + cont[:-1]
+
+
+def loglik_entries(ctx_lens: Sequence[int], conts: Sequence[Sequence[int]], stride: int, pos0: int = 0):
+    """Entry arrays of one scoring pass (`aur_llm_score_var`): sequence i of the pass holds positions [pos0, ctx_lens[i] + n_i - 1) of
+    a context of ctx_lens[i] SPLICED positions followed by conts[i][:-1], `stride` rows apart.  Token j of continuation i is scored
+    from position ctx_lens[i] - 1 + j, flat row i * stride + that position - pos0.
+    -> (rows int32, targets int32, [(first entry, entries)] per sequence)."""
+    rows, targets, spans = [], [], []
+    for i, (lc, cont) in enumerate(zip(ctx_lens, conts)):
+        n = len(cont)
+        first = int(lc) - 1 - pos0
+        if n < 1 or first < 0 or first + n > stride:
+            raise ValueError(f"sequence {i}: rows [{first}, {first + n}) of a continuation of {n} tokens outside its stride of {stride}")
+        spans.append((len(rows), n))
+        rows += [i * stride + first + j for j in range(n)]
+        targets += [int(t) for t in cont]
+    return np.asarray(rows, np.int32), np.asarray(targets, np.int32), spans
+
+
+def loglik_share_plan(plans: Sequence[dict], ctx_lens: Sequence[int], pixel_keys: Sequence, share: bool = True):
+    """Which items of a `loglikelihood_batch` chunk take the shared-prefix route: [(head, [(child, fork), ...])] in item order, every
+    item once.  A head runs the whole front end.  A child directly follows its head (or the head's earlier children), is about the
+    same pixels (equal `pixel_keys`), and its plan agrees with the head's through the last visual row (`share_fork`); its fork lies
+    at or below its first scored position ctx_len - 1, so every scored row belongs to the pass that starts at the fork."""
+    out: List[Tuple[int, List[Tuple[int, int]]]] = []
+    for i, plan in enumerate(plans):
+        if share and out:
+            h = out[-1][0]
+            if pixel_keys[h] is not None and pixel_keys[h] == pixel_keys[i]:
+                fork = min(share_fork(plans[h], plan), fork_point(int(ctx_lens[i]) - 1))
+                if fork > 0:
+                    out[-1][1].append((i, fork))
+                    continue
+        out.append((i, []))
+    return out
+
+
 class _PrefixHolders:
     """`caption_stream(share_key=)`'s cache: key -> the KV sequence that holds the leading pages of the first clip of that key, its
     kept visual rows and its splice plan.  Least recently used out.  Lives for one caption_stream call."""
@@ -702,6 +747,147 @@ class AuroraCapEngine:
         check(self.ctx, self.L.aur_copy_logits(self.ctx, out.data_ptr(), self._stream()), "aur_copy_logits")
         torch.cuda.synchronize()
         return out
+
+    # ------------------------------------------------------------------ scoring given continuations
+    def score_rows(self, logits: torch.Tensor, targets):
+        """The scoring kernel alone (aur_score_rows): logits fp32 [rows, vocab] on the device, one target per row (a list, or an int32
+        device tensor) -> (log-probabilities float32, first argmax int32) as numpy.  A target outside [0, vocab): (0, -1)."""
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) == logits.shape[1]
+        rows, vocab = logits.shape
+        tg = targets if torch.is_tensor(targets) else torch.tensor([int(t) for t in targets], dtype=torch.int32, device=self.dev)
+        assert tg.dtype == torch.int32 and tg.is_cuda and tg.numel() >= rows
+        lp = torch.empty(rows, dtype=torch.float32, device=self.dev)
+        am = torch.empty(rows, dtype=torch.int32, device=self.dev)
+        check(self.ctx, self.L.aur_score_rows(self.ctx, logits.data_ptr(), rows, vocab, tg.data_ptr(), lp.data_ptr(), am.data_ptr(), self._stream()),
+              "aur_score_rows")
+        torch.cuda.synchronize()
+        return lp.cpu().numpy(), am.cpu().numpy()
+
+    def _i32_arg(self, a, n: int, what: str) -> torch.Tensor:
+        if torch.is_tensor(a):
+            if a.dtype != torch.int32 or not a.is_cuda or not a.is_contiguous() or a.numel() < n:
+                raise ValueError(f"{what} must be a contiguous int32 device tensor of at least {n} entries")
+            return a
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev)
+        if t.numel() != n:
+            raise ValueError(f"{t.numel()} {what} for {n}")
+        self._tmp = getattr(self, "_tmp", [])[-64:] + [t]         # keep alive until consumed
+        return t
+
+    def score_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, pos0: int, stride: int, lens, rows, targets, *, nscore: Optional[int] = None,
+                    logprob_out: Optional[torch.Tensor] = None, argmax_out: Optional[torch.Tensor] = None,
+                    logits_out: Optional[torch.Tensor] = None, want_logits: bool = False):
+        """aur_llm_score_var: the layer stack of `prefill_stage(seq_lens=)` (pos0 == 0) or `extend_stage` (pos0 > 0) into KV sequences
+        [seq0, seq0 + nseq) with the last layer unpruned, then entry j - flat row rows[j] = i * stride + r of embeds, the hidden state
+        at position pos0 + r of sequence i - scored against targets[j]; a row of -1 is an unused entry.  lens / rows / targets: lists
+        (checked and uploaded here) or int32 device tensors (the caller's promise; `nscore` entries, default all of `rows`).
+        Enqueue-only: -> (logprob float32 [nscore], argmax int32 [nscore], logits fp32 [nscore, vocab] or None) on the device."""
+        if torch.is_tensor(lens):
+            lens_t = self._i32_arg(lens, nseq, "lens")
+        else:
+            ll = [int(x) for x in lens]
+            for x in ll:
+                if not 1 <= x <= stride or pos0 + x > self.c.max_ctx:
+                    raise ValueError(f"sequence of {x} rows at position {pos0}: outside [1, stride {stride}] or beyond max_ctx {self.c.max_ctx}")
+            lens_t = self._i32_arg(ll, nseq, "lens")
+        n = int(nscore) if nscore is not None else (rows.numel() if torch.is_tensor(rows) else len(rows))
+        rows_t, tg_t = self._i32_arg(rows, n, "score rows"), self._i32_arg(targets, n, "score targets")
+        vocab = self.l["vocab_size"]
+        lp = logprob_out if logprob_out is not None else torch.empty(n, dtype=torch.float32, device=self.dev)
+        am = argmax_out if argmax_out is not None else torch.empty(n, dtype=torch.int32, device=self.dev)
+        lg = logits_out if logits_out is not None else (torch.empty(n, vocab, dtype=torch.float32, device=self.dev) if want_logits else None)
+        assert lp.dtype == torch.float32 and am.dtype == torch.int32 and lp.numel() >= n and am.numel() >= n
+        assert lg is None or (lg.dtype == torch.float32 and lg.is_contiguous() and lg.numel() >= n * vocab)
+        if getattr(self, "_score_scratch", None) is None:
+            self._score_scratch = torch.empty(self.L.aur_score_scratch_bytes(self.ctx), dtype=torch.uint8, device=self.dev)
+        sc = self._score_scratch
+        check(self.ctx, self.L.aur_llm_score_var(self.ctx, seq0, nseq, embeds.data_ptr(), pos0, stride, lens_t.data_ptr(), rows_t.data_ptr(),
+                                                 tg_t.data_ptr(), n, sc.data_ptr(), sc.numel(), lp.data_ptr(), am.data_ptr(),
+                                                 lg.data_ptr() if lg is not None else None, self._stream()), "aur_llm_score_var")
+        return lp, am, lg
+
+    def loglikelihood_batch(self, items, token_kept_ratio: float, share: bool = True, prefill_group: int = 8) -> List[dict]:
+        """Log-likelihood of given continuations: items = [(pixel_values [f, C, H, W], context_ids with -200 markers, continuation_ids)]
+        -> per item dict(logprob = the sum of the tokens' log-probabilities (float64, token order), greedy = every continuation token
+        is the first argmax of its row, token_logprobs = [float], count = tokens) - `aurora_amd.scoring` is the definition.
+        Each sequence is laid out as context + continuation[:-1] and runs through ONE prefill pass whose rows ctx_len - 1 .. are
+        scored (`score_stage`); neighbours whose lengths round up to the same stride share a pass (`prefill_groups`).  An empty
+        continuation is (0.0, True) with no GPU work.  Calls `begin_batch` itself, like `caption_batch`: not meant to run beside a
+        live `caption_stream`.  ValueError when a sequence does not fit max_ctx.
+        share=True: neighbouring items about the same pixels tensor whose plans agree through the last visual row (several candidate
+        answers to one question about one clip) take the shared-prefix route - the first runs the whole front end, the others copy
+        the common KV pages from it (`kv_copy_prefix`) and are scored in one pass that starts at the fork (`loglik_share_plan`).
+        Bitwise the result of share=False."""
+        from . import scoring
+        results: List[Optional[dict]] = [None] * len(items)
+        live = []
+        for i, (px, ctx_ids, cont) in enumerate(items):
+            cont = [int(t) for t in cont]
+            if not cont:
+                results[i] = dict(logprob=0.0, greedy=True, token_logprobs=[], count=0)
+            else:
+                live.append((i, px, loglik_ids(ctx_ids, cont), cont))
+        d = self.l["hidden_size"]
+        bucket = self.prompt_bucket or 32                          # a scoring pass is always the strided form
+        for c0 in range(0, len(live), self.max_batch):
+            chunk = live[c0:c0 + self.max_batch]
+            rs, plans, ctx_lens = [], [], []
+            for _, px, ids, cont in chunk:
+                r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
+                t0 = (px.shape[-2] // self.v["patch_size"]) * (px.shape[-1] // self.v["patch_size"]) + 1     # as vit_encode counts them
+                plan = self.splice_plan(ids, px.shape[0], tokens_at_layer(t0, r, self.v["num_hidden_layers"] - 1) - 1)
+                if plan["seq_len"] > self.c.max_ctx:
+                    raise ValueError(f"context + continuation of {plan['seq_len']} positions exceeds max_ctx {self.c.max_ctx}")
+                rs.append(r)
+                plans.append(plan)
+                ctx_lens.append(plan["seq_len"] - (len(cont) - 1))
+            conts = [c[3] for c in chunk]
+            keys = [(c[1].data_ptr(), tuple(c[1].shape)) for c in chunk]
+            groups = loglik_share_plan(plans, ctx_lens, keys, share)
+            heads = [h for h, _ in groups]
+            seq_of = {h: k for k, h in enumerate(heads)}           # KV sequences: the heads first, then the children, both in item order
+            for _, kids in groups:
+                for c, _ in kids:
+                    seq_of[c] = len(seq_of)
+            keep_vis = {h for h, kids in groups if kids}
+            vis_of, pending = {}, []
+            self.begin_batch(len(chunk), 1, None)
+            for b, g, stride in prefill_groups([plans[h]["seq_len"] for h in heads], prefill_group, bucket):
+                members = heads[b:b + g]
+                buf = torch.empty(g * stride, d, dtype=torch.float16, device=self.dev)
+                for k, h in enumerate(members):
+                    vis = self.vit_encode(chunk[h][1], rs[h])
+                    if h in keep_vis:
+                        vis_of[h] = vis
+                    self.project_splice(vis, out=buf[k * stride:(k + 1) * stride], plan=plans[h])
+                rows, tg, spans = loglik_entries([ctx_lens[h] for h in members], [conts[h] for h in members], stride)
+                lp, am, _ = self.score_stage(seq_of[members[0]], g, buf, 0, stride, [plans[h]["seq_len"] for h in members], rows, tg)
+                pending.append((members, spans, lp, am, buf))
+            for h, kids in groups:
+                k0 = 0
+                while k0 < len(kids):                              # neighbouring children of one fork: one copy, one pass
+                    fork, g = kids[k0][1], 1
+                    while k0 + g < len(kids) and kids[k0 + g][1] == fork and g < prefill_group:
+                        g += 1
+                    members = [c for c, _ in kids[k0:k0 + g]]
+                    new = [plans[c]["seq_len"] - fork for c in members]
+                    stride = _rup(max(new), 32)
+                    buf = torch.empty(g * stride, d, dtype=torch.float16, device=self.dev)
+                    for k, c in enumerate(members):
+                        self._extend_rows(vis_of[h], plans[c], fork, buf[k * stride:(k + 1) * stride])
+                    self.kv_copy_prefix(seq_of[h], seq_of[members[0]], g, fork)
+                    rows, tg, spans = loglik_entries([ctx_lens[c] for c in members], [conts[c] for c in members], stride, fork)
+                    lp, am, _ = self.score_stage(seq_of[members[0]], g, buf, fork, stride, new, rows, tg)
+                    pending.append((members, spans, lp, am, buf))
+                    k0 += g
+            torch.cuda.synchronize()
+            for members, spans, lp, am, _ in pending:
+                lp, am = lp.cpu().numpy(), am.cpu().numpy()
+                for m, (e0, n) in zip(members, spans):
+                    greedy = bool((am[e0:e0 + n] == np.asarray(conts[m], np.int32)).all())
+                    total, greedy, lps = scoring.combine(lp[e0:e0 + n].tolist(), greedy)
+                    results[chunk[m][0]] = dict(logprob=total, greedy=greedy, token_logprobs=lps, count=n)
+        return results
 
     # ------------------------------------------------------------------ sampling
     def _sampling_on(self):

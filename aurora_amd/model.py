@@ -148,6 +148,16 @@ class AuroraModel:
             out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 
+    def loglikelihood_batch(self, items, share: bool = True):
+        """Log-likelihood of given continuations: items = [(pixel_values [f, c, h, w], context ids with -200 markers, continuation
+        ids)] -> per item dict(logprob, greedy, token_logprobs, count), in order (AuroraCapEngine.loglikelihood_batch; it cuts
+        the items into chunks of max_batch itself).  Uses visual_encoder.visual_token_merge_ratio.  A slow-fast model raises."""
+        if self.slowfast:
+            raise NotImplementedError("loglikelihood_batch on a slow-fast model (ragged per-frame token counts)")
+        as_list = lambda ids: ids.tolist() if torch.is_tensor(ids) else list(ids)      # noqa: E731
+        return self.engine.loglikelihood_batch([(px, as_list(c), as_list(t)) for px, c, t in items],
+                                               self.visual_encoder.visual_token_merge_ratio, share=share)
+
     def caption_prompts(self, pixel_values, list_of_input_ids, max_new_tokens: int = 2048, eos_token_id="default", sampling=None,
                         streams=None):
         """One clip, several prompts (the five VDC questions about a video): pixel_values [f, c, h, w], each prompt's input ids with

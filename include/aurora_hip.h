@@ -243,7 +243,7 @@ int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_d
  * graph's static buffers before every replay: src/sglang/python/sglang/srt/model_executor/cuda_graph_runner.py:163-279) ------------
  * aur_graph_begin opens a hipGraph capture on `stream` (thread-local mode); every enqueue-only call of this ctx that follows on that
  * stream from the same thread - aur_vit_encode(_hw), aur_project_splice(_var), aur_llm_prefill / _batch / _stage / _commit (and their _var forms),
- * aur_kv_copy_prefix, aur_llm_extend_*_var, aur_slot_reset /
+ * aur_kv_copy_prefix, aur_llm_extend_*_var, aur_llm_score_var, aur_slot_reset /
  * _retire / _collect, the kernel-level entry points - is recorded instead of run; aur_graph_end instantiates the recording and returns
  * a handle (>= 1) that aur_graph_launch replays with one call.  Pointers, shapes, KV sequence ids, the ctx's gemm_* knobs and the
  * current bank (whose page table the prefill writes through) are frozen at capture time: a serving loop keeps one graph per (bank,
@@ -306,6 +306,31 @@ int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
  * of the kept set). */
 int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const aur_sampling* params_dev,
                     const int32_t* n_dev, int32_t* tokens_out, int32_t* kept_out, void* stream);
+
+/* ---- scoring given continuations (lmms-eval's `loglikelihood` request) ---------------------------------------
+ * aur_score_rows: the kernel alone on caller rows.  logits fp32 [rows, vocab] device; targets_dev int32 [rows].  Per row, with a =
+ * the first index of the maximum m: logprob_out = (l[target] - m) - log(sum exp(l[i] - m)) in fp32 and argmax_out = a - a pure function
+ * of the row's values (the same bits at any row index, row count or alignment).  A target outside [0, vocab) marks an unused entry:
+ * logprob 0, argmax -1, the row is not read.  aurora_amd/scoring.py is the definition in numpy.
+ * aur_llm_score_var: the layer stack of aur_llm_prefill_stage_var (pos0 == 0) or aur_llm_extend_stage_var (pos0 a positive multiple of
+ * the 64-token page) over KV sequences [seq0, seq0 + nseq) - same argument checks, same clearing of the padding rows, the K / V of
+ * every position written, no decode state touched (on spare sequences it may sit between two aur_llm_decode calls) - except that the
+ * last layer always runs unpruned; then nscore_cap entries are scored, in chunks of max_batch, through the pick path's lm_head (folded
+ * final norm) and the kernel above, on the caller's scratch (aur_score_scratch_bytes, 256-byte aligned; a function of the config
+ * alone).  Entry j names flat row score_rows_dev[j] = i * stride + r of embeds - the hidden state at position pos0 + r of sequence i -
+ * and the target score_targets_dev[j] it is scored against.  A row < 0, outside nseq * stride or at / beyond its sequence's clamped
+ * length, or a target outside [0, vocab), marks an unused entry (logprob 0, argmax -1).  logits_out: fp32 [nscore_cap, vocab] or
+ * NULL (tests; rows of unused entries are unspecified).  The host reads none of the device arrays: enqueue-only, recordable with
+ * aur_graph_begin; a capture freezes the capacity and the pointers, not the values.
+ * CONTRACT: for an entry naming row r of sequence i the logits row is BITWISE what aur_copy_logits returns after
+ * aur_llm_prefill(slot, embeds_i[0 .. pos0 + r], pos0 + r + 1) on the same ctx, argmax_out is that prefill's greedy first token, and
+ * logprob_out / argmax_out are bitwise what aur_score_rows gives on that row. */
+int64_t aur_score_scratch_bytes(const aur_ctx* ctx);
+int aur_llm_score_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride, const int32_t* lens_dev,
+                      const int32_t* score_rows_dev, const int32_t* score_targets_dev, int32_t nscore_cap, void* scratch,
+                      int64_t scratch_bytes, float* logprob_out, int32_t* argmax_out, float* logits_out, void* stream);
+int aur_score_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* targets_dev, float* logprob_out,
+                   int32_t* argmax_out, void* stream);
 
 /* Tuning knobs.  Invalidate the captured decode graphs (of every bank): "decode_fused_reduce" 0 (default: the split-K residual projections are followed
  * by a reduce launch) / 1 (the last-arriving split reduces inside the kernel; bitwise the same), "dec_attn_local" 1 (default: on engines

@@ -44,6 +44,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--extra_prompt', action='append', default=[], metavar='TEXT',
                         help='a further instruction about the same visual input (repeatable): one more caption is printed per flag, in order; '
                              'with --synthetic there is no tokenizer: the text is ignored and each flag adds a seeded prompt of its own length')
+    parser.add_argument('--score', default=None, metavar='TEXT',
+                        help='instead of generating: print the log-likelihood of TEXT as the answer to --prompt (the sum of its tokens\' '
+                             'log-probabilities), with is_greedy (every token of TEXT is the greedy pick) and the token count; '
+                             'with --synthetic there is no tokenizer: the text is ignored and a seeded answer of 8 tokens is scored')
     return parser
 
 
@@ -120,6 +124,17 @@ def main():
                                             max_new_tokens=args.max_new_tokens, max_batch=1 + len(extra_ids))
 
     model.visual_encoder.reset_tome_r(args.token_kept_ratio)
+    if args.score is not None:        # how likely is this answer: one pass over prompt + answer, the answer's rows scored
+        px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
+        ctx_ids = data["input_ids"][0].tolist()
+        if tokenizer is None:
+            cont_ids = np.random.default_rng(4000).integers(3, 32000, size=8).tolist()
+        else:                         # the answer as the prompt's continuation: the ids the full text adds behind the prompt's
+            full = process_text(build_prompt(args.prompt, n_img) + args.score, tokenizer)[0].tolist()
+            cont_ids = full[len(ctx_ids):]
+        r = model.loglikelihood_batch([(px, ctx_ids, cont_ids)])[0]
+        print(f"loglikelihood {r['logprob']:.6f} is_greedy {r['greedy']} tokens {r['count']}")
+        return
     if extra_ids:                     # several prompts about one input: one caption per prompt, in order
         px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
         samp = dict(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=args.seed) if args.do_sample else None
