@@ -103,6 +103,9 @@ SIGNATURES = {
     "aur_vit_layer": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aur_slot_sampling": (C.c_int, [_P, _I, _I, _P, _P]),
     "aur_sample_rows": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "aur_attn_rows": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "aur_attn_decode_scratch_bytes": (_L, [_P, _I]),
+    "aur_attn_decode_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _L, _P, _P]),
     "aur_copy_logits": (C.c_int, [_P, _P, _P]),
     "aur_score_scratch_bytes": (_L, [_P]),
     "aur_llm_score_var": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P]),

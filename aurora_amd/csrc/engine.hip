@@ -17,6 +17,7 @@
 
 #include "../../include/aurora_hip.h"
 #include "kernels.h"
+#include "advance.h"      // xfrag_piece
 
 struct Tensor {
     const void* p;
@@ -1435,6 +1436,103 @@ static SkinnyArgs mk_dec_down(aur_ctx* ctx, int l) {
     dn.variant = ctx->skinny_variant; dn.part = (g.llm_mlp >= ctx->row_split_min_k || g.max_batch > 64) ? ctx->d_part_row : nullptr;
     dn.row_cnt = ctx->fused_reduce ? ctx->d_row_cnt : nullptr; dn.half_grid = ctx->decode_half;
     return dn;
+}
+
+// ---- the attention kernels alone on caller rows (parity tests): the production fragment writer - the QKV epilogue of the layer - then the
+// production attention launch, nothing else.  With x = [q | k | v] and the identity as weight (packed with the loader's row map) the
+// fragments hold exactly the caller's q, k, v: fp16 x 1.0 accumulated in fp32 is exact.
+extern "C" int aur_attn_rows(aur_ctx* ctx, int32_t layout, const void* x, int32_t nseq, int32_t rows, int32_t kx, const void* w_packed,
+                             int32_t npad, const float* bias, int32_t seq0, int32_t rope, int32_t t, const int32_t* lens_dev, int32_t causal,
+                             void* out, void* stream) {
+    const char* who = "aur_attn_rows";
+    if (!ctx || !x || !w_packed || !out) return aur_fail(ctx, AUR_ERR_ARG, "%s: null argument", who);
+    if (layout != AUR_ATTN_VIT && layout != AUR_ATTN_LLM) return aur_fail(ctx, AUR_ERR_ARG, "%s: layout %d is neither AUR_ATTN_VIT nor AUR_ATTN_LLM", who, layout);
+    if (!ctx->ws) return aur_fail(ctx, AUR_ERR_STATE, "%s: workspace not set", who);
+    if (nseq < 1 || rows < 32 || (rows & 31) || kx < 64 || (kx & 63))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: need nseq >= 1, rows a positive multiple of 32, kx a positive multiple of 64 (got %d, %d, %d)", who, nseq, rows, kx);
+    if (!lens_dev && (t < 1 || t > rows)) return aur_fail(ctx, AUR_ERR_ARG, "%s: t %d outside [1, rows %d]", who, t, rows);
+    const aur_config& g = ctx->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    GemmArgs q{};
+    q.A = (const half_t*)x; q.lda = kx; q.W = (const half_t*)w_packed; q.bias = bias; q.M = nseq * rows; q.Npad = npad; q.K = kx;
+    q.rows_per_seq = rows; q.pos0 = 0;
+    AttnArgs at{};
+    at.nseq = nseq; at.rows_per_seq = rows; at.t = lens_dev ? rows : t; at.causal = causal ? 1 : 0; at.O = (half_t*)out;
+    at.seq_lens = lens_dev; at.len_cap = rows;
+    if (layout == AUR_ATTN_VIT) {
+        if (seq0 != 0 || rope) return aur_fail(ctx, AUR_ERR_ARG, "%s: the ViT layout has no page table and no RoPE (seq0 %d, rope %d)", who, seq0, rope);
+        if (nseq > g.max_frames || rows > ctx->v_t0pad) return aur_fail(ctx, AUR_ERR_ARG, "%s: %d sequences of %d rows exceed the workspace (%d frames of %d rows)", who, nseq, rows, g.max_frames, ctx->v_t0pad);
+        if (npad != ctx->v_qkv_npad) return aur_fail(ctx, AUR_ERR_ARG, "%s: npad %d is not the ViT's packed QKV width %d", who, npad, ctx->v_qkv_npad);
+        q.q_cols = ctx->v_qcols; q.k_cols = ctx->v_qcols; q.hd = ctx->v_hd; q.Qf = ctx->w_qf; q.kv = vit_kv(ctx, rows); q.rope = nullptr; q.seq0 = 0;
+        q.tag = GT_VIT_QKV;
+        at.heads = g.vit_heads; at.hd = ctx->v_hd;
+    } else {
+        if (!ctx->finalized || ctx->ll.empty() || !ctx->kvpool) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
+        if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d)", who, seq0, seq0 + nseq, ctx->kv_seqs);
+        if (rows > ctx->l_ctx_pad || (int64_t)nseq * rows > (int64_t)ctx->l_ctx_pad * g.max_batch)
+            return aur_fail(ctx, AUR_ERR_ARG, "%s: %d sequences of %d rows exceed the workspace (%d sequences of %d positions)", who, nseq, rows, g.max_batch, ctx->l_ctx_pad);
+        if (npad != ctx->l_qkv_npad) return aur_fail(ctx, AUR_ERR_ARG, "%s: npad %d is not the language model's packed QKV width %d", who, npad, ctx->l_qkv_npad);
+        q.q_cols = g.llm_hidden; q.k_cols = g.llm_hidden; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, 0);
+        q.rope = rope ? ctx->l_rope : nullptr; q.seq0 = seq0; q.tag = GT_LLM_QKV;
+        at.heads = g.llm_heads; at.hd = ctx->l_hd;
+    }
+    at.Qf = q.Qf; at.kv = q.kv; at.seq0 = q.seq0; at.scale = 1.0f / sqrtf((float)at.hd); at.ldo = at.heads * at.hd;
+    CK(ctx_gemm(ctx, q, EPI_QKV, s));
+    CK(launch_attention(at, s));
+    return AUR_OK;
+}
+
+// The decode step's attention alone: x fragments of the caller's rows, the step's QKV projection (RoPE, K / V written at pos[b] into layer
+// 0 of the selected bank's pages of sequence b), then the decode attention exactly as mk_dec_attn sets it up.  Scratch (the caller's):
+// x fragments of round_up(max_batch, 16) rows of kx columns | a (cos, sin) = (1, 0) table for rope == 0 (x * 1 - y * 0 is exact).
+__global__ void rope_identity_kernel(float2* __restrict__ tab, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) tab[i] = make_float2(1.f, 0.f);
+}
+__global__ void xfrag_unpack_kernel(const half_t* __restrict__ xf, int rows, int d, half_t* __restrict__ out) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x, nchunk = d >> 3;
+    if (id >= rows * nchunk) return;
+    const int b = id / nchunk, k = (id % nchunk) * 8;
+    *(h8*)(out + (int64_t)b * d + k) = *(const h8*)(xf + xfrag_piece(b, k, d >> 5));
+}
+static int64_t attn_dec_xf_bytes(const aur_ctx* c, int kx) { return rup64((int64_t)rup(c->cfg.max_batch, 16) * kx * 2, 256); }
+extern "C" int64_t aur_attn_decode_scratch_bytes(const aur_ctx* ctx, int32_t kx) {
+    if (!ctx || kx < 1) return 0;
+    return attn_dec_xf_bytes(ctx, kx) + rup64((int64_t)ctx->l_ctx_pad * (ctx->l_hd / 2) * (int64_t)sizeof(float2), 256);
+}
+extern "C" int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, const void* w_packed, int32_t npad,
+                                    const int32_t* pos_dev, int32_t rope, void* scratch, int64_t scratch_bytes, void* out, void* stream) {
+    const char* who = "aur_attn_decode_rows";
+    if (!ctx || !x || !w_packed || !pos_dev || !out) return aur_fail(ctx, AUR_ERR_ARG, "%s: null argument", who);
+    if (!ctx->finalized || ctx->ll.empty() || !ctx->kvpool) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
+    const aur_config& g = ctx->cfg;
+    if (rows < 1 || rows > g.max_batch || kx < 128 || (kx & 127)) return aur_fail(ctx, AUR_ERR_ARG, "%s: need 1 <= rows <= max_batch %d and kx a positive multiple of 128 (got %d, %d)", who, g.max_batch, rows, kx);
+    if (npad != ctx->l_qkv_npad) return aur_fail(ctx, AUR_ERR_ARG, "%s: npad %d is not the language model's packed QKV width %d", who, npad, ctx->l_qkv_npad);
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < aur_attn_decode_scratch_bytes(ctx, kx))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: scratch must be 256-byte aligned and hold aur_attn_decode_scratch_bytes = %lld bytes (got %lld)", who,
+                        (long long)aur_attn_decode_scratch_bytes(ctx, kx), (long long)scratch_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const int d = g.llm_hidden;
+    half_t* xf = (half_t*)scratch;
+    float2* ident = (float2*)((char*)scratch + attn_dec_xf_bytes(ctx, kx));
+    CK(hipMemsetAsync(xf, 0, (size_t)rup(rows, 16) * kx * 2, s));          // lanes of unused rows of the last group hold finite values
+    CK(launch_xfrag_pack((const half_t*)x, kx, rows, kx, xf, s));
+    if (!rope) {
+        const int n = ctx->l_ctx_pad * (ctx->l_hd / 2);
+        hipLaunchKernelGGL(rope_identity_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ident, n);
+        CK(hipGetLastError());
+    }
+    SkinnyArgs q{};      // as mk_dec_qkv sets it up, without the folded norm, on the caller's rows and positions
+    q.xf = xf; q.W = (const half_t*)w_packed; q.B = rows; q.b_lo = 0; q.b_hi = rows; q.Npad = npad; q.K = kx; q.n_real = 3 * d; q.mode = SK_QKV;
+    q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.qbuf = ctx->d_q; q.kv = llm_kv(ctx, 0); q.rope = rope ? ctx->l_rope : ident; q.pos = pos_dev;
+    q.seq_ids = nullptr; q.variant = ctx->skinny_variant_wide; q.half_grid = ctx->decode_half;
+    CK(launch_skinny(q, s));
+    DecAttnArgs at = mk_dec_attn(ctx, 0);
+    at.pos = pos_dev; at.B = rows;
+    CK(launch_decode_attention(at, s));
+    hipLaunchKernelGGL(xfrag_unpack_kernel, dim3((rows * (d >> 3) + 255) / 256), dim3(256), 0, s, ctx->d_attn, rows, d, (half_t*)out);
+    CK(hipGetLastError());
+    return AUR_OK;
 }
 
 // One thread stores the device's constant-rate clock (wall_clock64: hipDeviceAttributeWallClockRate kHz) for step `n` = ring[0];

@@ -442,12 +442,7 @@ class AuroraCapEngine:
         dpad, mpad = _rup(D, 256), _rup(mlp, 256)
         P, Cn = v["patch_size"], v.get("num_channels", 3)
         kpad = _rup(Cn * P * P, 64)
-        # fused QKV row map: Q and K heads padded hd -> hd_pad (zero rows), V natural
-        rm = np.full(npad, -1, np.int32)
-        for h in range(H):
-            rm[h * hdp: h * hdp + hd] = np.arange(h * hd, (h + 1) * hd)
-            rm[qcols + h * hdp: qcols + h * hdp + hd] = D + np.arange(h * hd, (h + 1) * hd)
-        rm[2 * qcols: 2 * qcols + D] = 2 * D + np.arange(D)
+        rm = self.vit_qkv_row_map(D, H, npad)
         self._set("vit.patch.w", self.pack(w["patch_embedding.weight"].reshape(D, -1), dpad, kpad))
         self._set("vit.cls", self._h(w["class_embedding"].reshape(-1)))
         self._pos_cache: Dict[tuple, torch.Tensor] = {}                  # interpolated_pos(): one table per input size
@@ -472,6 +467,19 @@ class AuroraCapEngine:
             self._set(p + "fc1.b", self._bias(lw["fc1.bias"], mpad))
             self._set(p + "fc2.w", self.pack(lw["fc2.weight"], dpad, mlp))
             self._set(p + "fc2.b", self._bias(lw["fc2.bias"], dpad))
+
+    @staticmethod
+    def vit_qkv_row_map(D: int, heads: int, npad: int) -> np.ndarray:
+        """fused QKV row map of the vision tower: Q and K heads padded hd -> hd_pad (zero rows), V natural"""
+        hd = D // heads
+        hdp = _rup(hd, 32)
+        qcols = _rup(heads * hdp, 64)
+        rm = np.full(npad, -1, np.int32)
+        for h in range(heads):
+            rm[h * hdp: h * hdp + hd] = np.arange(h * hd, (h + 1) * hd)
+            rm[qcols + h * hdp: qcols + h * hdp + hd] = D + np.arange(h * hd, (h + 1) * hd)
+        rm[2 * qcols: 2 * qcols + D] = 2 * D + np.arange(D)
+        return rm
 
     @staticmethod
     def llama_qkv_row_map(d: int, heads: int, npad: int) -> np.ndarray:
@@ -1514,6 +1522,50 @@ class AuroraCapEngine:
                                              sr.data_ptr(), ds.data_ptr(), self._stream()), "aur_vit_layer")
         torch.cuda.synchronize()
         return xo, so, me, dict(r=rl, node_idx=ni, unm_idx=un[:, : ta - rl], src_idx=sr[:, :rl], dst_idx=ds[:, :rl])
+
+    def attn_identity_weight(self, layout: str) -> torch.Tensor:
+        """the identity [3 D, 3 D] packed with the loader's QKV row map of `layout` ("vit" / "llm"): with x = [q | k | v] the QKV
+        epilogue then writes exactly the caller's q, k, v into the attention's fragments"""
+        m = self.v if layout == "vit" else self.l
+        D, H = m["hidden_size"], m["num_attention_heads"]
+        if layout == "vit":
+            npad = _rup(2 * _rup(H * _rup(D // H, 32), 64) + D, 256)
+            rm = self.vit_qkv_row_map(D, H, npad)
+        else:
+            npad = _rup(3 * D, 256)
+            rm = self.llama_qkv_row_map(D, H, npad)
+        return self.pack(torch.eye(3 * D), npad, 3 * D, rm)
+
+    def attn_rows(self, x: torch.Tensor, w_packed: torch.Tensor, *, layout: str, nseq: int, rows: int, causal: bool, t: Optional[int] = None,
+                  lens=None, rope: bool = False, seq0: int = 0, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """aur_attn_rows: the QKV epilogue + attn_kernel on caller rows x [nseq * rows, kx]; `t` valid keys / queries by value, or `lens`
+        (one per sequence) through device memory.  Returns fp16 [nseq * rows, heads * head_dim]."""
+        m = self.v if layout == "vit" else self.l
+        xh = self._h(x)
+        kx = xh.shape[1]
+        assert xh.shape[0] == nseq * rows and (t is None) != (lens is None)
+        lens_t = self._i32_arg(lens, nseq, "lens") if lens is not None else None
+        out = torch.empty(nseq * rows, m["hidden_size"], dtype=torch.float16, device=self.dev)
+        check(self.ctx, self.L.aur_attn_rows(self.ctx, 0 if layout == "vit" else 1, xh.data_ptr(), nseq, rows, kx, w_packed.data_ptr(),
+                                             w_packed.numel() // kx, bias.data_ptr() if bias is not None else None, seq0, int(rope),
+                                             int(t or 0), lens_t.data_ptr() if lens_t is not None else None, int(causal), out.data_ptr(),
+                                             self._stream()), "aur_attn_rows")
+        torch.cuda.synchronize()
+        return out
+
+    def attn_decode_rows(self, x: torch.Tensor, w_packed: torch.Tensor, pos, *, rope: bool = False) -> torch.Tensor:
+        """aur_attn_decode_rows: one decode step's QKV write + decode attention on caller rows x [B, kx]; pos[b] = tokens already cached
+        for KV sequence b.  Returns fp16 [B, hidden]."""
+        xh = self._h(x)
+        B, kx = xh.shape
+        pos_t = self._i32_arg(pos, B, "pos")
+        scratch = torch.empty(self.L.aur_attn_decode_scratch_bytes(self.ctx, kx), dtype=torch.uint8, device=self.dev)
+        out = torch.empty(B, self.l["hidden_size"], dtype=torch.float16, device=self.dev)
+        check(self.ctx, self.L.aur_attn_decode_rows(self.ctx, xh.data_ptr(), B, kx, w_packed.data_ptr(), w_packed.numel() // kx,
+                                                    pos_t.data_ptr(), int(rope), scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                                    self._stream()), "aur_attn_decode_rows")
+        torch.cuda.synchronize()
+        return out
 
     def set_option(self, name: str, value: int):
         check(self.ctx, self.L.aur_set_option(self.ctx, name.encode(), int(value)), "aur_set_option")

@@ -298,6 +298,30 @@ int aur_vit_layer(aur_ctx* ctx, int32_t layer, const void* x, const float* size,
                   int32_t r, void* x_out, float* size_out, float* metric_out, int32_t* node_idx,
                   int32_t* unm_idx, int32_t* src_idx, int32_t* dst_idx, void* stream);
 
+/* The attention kernels alone on caller rows (tests/test_gpu_attention.py): the layer's own fragment writer, then its attention launch.
+ * aur_attn_rows: launch_gemm(EPI_QKV) + launch_attention (attn_kernel: ViT and causal prefill).  x fp16 [nseq * rows, kx] (kx % 64 == 0),
+ * w_packed [npad, kx] from aur_pack_linear with the loader's QKV row map (npad = the model's packed QKV width), bias fp32 [npad] or NULL.
+ * With x = [q | k | v] and the identity as weight the fragments hold exactly the caller's q, k, v.  layout AUR_ATTN_VIT: one page per
+ * sequence in the workspace, the ctx's ViT head geometry, seq0 = rope = 0, nseq <= max_frames, rows <= the padded token capacity;
+ * AUR_ATTN_LLM: layer 0 of the KV pool through the selected bank's page table, KV sequences [seq0, seq0 + nseq), positions [0, rows),
+ * RoPE on (rope = 1) or off.  rows: a multiple of 32, >= round_up(t, 32).  Valid keys / queries per sequence: t by value (lens_dev ==
+ * NULL), or lens_dev int32 [nseq] in device memory, clamped into [1, rows] (the AttnArgs seq_lens path: output rows at or beyond a
+ * sequence's length are zeros).  out fp16 [nseq * rows, heads * head_dim] row-major.  K / V of all `rows` positions stay in the pages
+ * (they feed aur_attn_decode_rows); no decode state is touched.  Bad arguments: AUR_ERR_ARG, the ctx stays usable.
+ * aur_attn_decode_rows: launch_xfrag_pack + launch_skinny(SK_QKV) + launch_decode_attention (decode_attn_dot_kernel, decode_attn_combine_kernel)
+ * with the split geometry of the decode step ("dec_attn_pps", "dec_attn_local").  x fp16 [rows, kx] (rows <= max_batch, kx % 128 == 0);
+ * pos_dev int32 [rows] in device memory: tokens already cached for KV sequence b of the selected bank - the step writes its K / V at
+ * position pos[b] (< the positions of a sequence's pages: the CALLER'S promise, the host never reads it) and attends to keys [0, pos[b]].
+ * out fp16 [rows, hidden] row-major.  scratch: aur_attn_decode_scratch_bytes(ctx, kx) bytes, 256-byte aligned.  Uses the decode step's
+ * query / partial / output scratch of the workspace: not beside a running aur_llm_decode. */
+#define AUR_ATTN_VIT 0
+#define AUR_ATTN_LLM 1
+int aur_attn_rows(aur_ctx* ctx, int32_t layout, const void* x, int32_t nseq, int32_t rows, int32_t kx, const void* w_packed, int32_t npad,
+                  const float* bias, int32_t seq0, int32_t rope, int32_t t, const int32_t* lens_dev, int32_t causal, void* out, void* stream);
+int64_t aur_attn_decode_scratch_bytes(const aur_ctx* ctx, int32_t kx);
+int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, const void* w_packed, int32_t npad, const int32_t* pos_dev,
+                         int32_t rope, void* scratch, int64_t scratch_bytes, void* out, void* stream);
+
 /* Copy the last-position logits of the most recent prefill / decode step into dst_dev: fp32 [batch, vocab]. */
 int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
 
