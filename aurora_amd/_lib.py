@@ -106,6 +106,8 @@ SIGNATURES = {
     "aur_attn_rows": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
     "aur_attn_decode_scratch_bytes": (_L, [_P, _I]),
     "aur_attn_decode_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _L, _P, _P]),
+    "aur_decode_proj_scratch_bytes": (_L, [_P, _I, _I]),
+    "aur_decode_proj_rows": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _I, _I, C.c_float, C.c_float, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
     "aur_copy_logits": (C.c_int, [_P, _P, _P]),
     "aur_score_scratch_bytes": (_L, [_P]),
     "aur_llm_score_var": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P]),

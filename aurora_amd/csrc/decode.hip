@@ -113,9 +113,10 @@ __device__ __forceinline__ void skinny_store(const SkinnyArgs& a, const int tile
                 if (MODE == SK_LOGITS) {
                     float* dst = a.out32 + (int64_t)b * a.n_real + n;
                     if ((a.n_real & 3) == 0) *(f4*)dst = acc[t][nb];      // n % 4 == 0: one 16-byte store
-                    else {
+                    else {      // ragged row end: column n + i exists only below n_real (the next address is column 0 of row b + 1)
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) dst[i] = acc[t][nb][i];
+                        for (int i = 0; i < 4; ++i)
+                            if (n + i < a.n_real) dst[i] = acc[t][nb][i];
                     }
                 } else if (MODE == SK_SILU_MUL) {
                     // h[b][k], k = n/2 + {0,1} = tile*8 + 2g + {0,1}, written in x-fragment form for the down projection

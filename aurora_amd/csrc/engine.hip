@@ -852,8 +852,8 @@ extern "C" int aur_linear(aur_ctx* ctx, const void* a, int32_t m, int32_t k, con
 }
 extern "C" int aur_linear_skinny(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                                  int32_t n, float* out, void* stream) {
-    if (m < 1 || m > AUR_MAX_BATCH || (k & 127) || k > 16384 || (npad & 31) || n > npad || (n & 3))
-        return aur_fail(ctx, AUR_ERR_ARG, "aur_linear_skinny: need m <= %d, k %% 128 == 0, k <= 16384", AUR_MAX_BATCH);
+    if (m < 1 || m > AUR_MAX_BATCH || (k & 127) || k > 16384 || (npad & 31) || n < 1 || n > npad)       // any n: a ragged row end is stored column by column
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_linear_skinny: need m <= %d, k %% 128 == 0, k <= 16384, 1 <= n <= npad", AUR_MAX_BATCH);
     if (!ctx->ws) return aur_fail(ctx, AUR_ERR_STATE, "aur_linear_skinny: workspace not set");
     hipStream_t st = (hipStream_t)stream;
     CK(hipMemsetAsync(ctx->d_scr, 0, (size_t)AUR_MAX_BATCH * 16384 * 2, st));
@@ -1532,6 +1532,85 @@ extern "C" int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, i
     CK(launch_decode_attention(at, s));
     hipLaunchKernelGGL(xfrag_unpack_kernel, dim3((rows * (d >> 3) + 255) / 256), dim3(256), 0, s, ctx->d_attn, rows, d, (half_t*)out);
     CK(hipGetLastError());
+    return AUR_OK;
+}
+
+// One decode projection alone on caller rows (parity tests): the production producer of x fragments (and sum(x^2)) at batch rows
+// [b0, b0 + rows), then launch_skinny in the structure the decode step would pick for this engine - variant, split-K partials, fused
+// reduce, k phases of gate/up, half grid exactly as mk_dec_o / mk_dec_down / mk_dec_gateup / the lm_head set them.  Everything else is
+// copies between the caller's row-major buffers and the fragment forms.  Scratch (the caller's): x fragments of round_up(max_batch, 16)
+// rows | residual / SiLU*up fragments | split-K partials | arrival counters.
+static int64_t proj_rows_pad(const aur_ctx* c) { return rup(c->cfg.max_batch, 16); }
+static int64_t proj_xf_bytes(const aur_ctx* c, int k) { return rup64(proj_rows_pad(c) * k * 2, 256); }
+static int64_t proj_frag_bytes(const aur_ctx* c, int npad) { return rup64(proj_rows_pad(c) * npad * 2, 256); }
+static int64_t proj_part_bytes(const aur_ctx* c, int npad) { return rup64((int64_t)4 * (npad / 16) * (proj_rows_pad(c) / 16) * 1024, 256); }
+extern "C" int64_t aur_decode_proj_scratch_bytes(const aur_ctx* ctx, int32_t k, int32_t npad) {
+    if (!ctx || k < 1 || npad < 16) return 0;
+    return proj_xf_bytes(ctx, k) + proj_frag_bytes(ctx, npad) + proj_part_bytes(ctx, npad) + rup64((int64_t)(npad / 16) * 4, 256);
+}
+extern "C" int aur_decode_proj_rows(aur_ctx* ctx, int32_t mode, const void* x, int32_t rows, int32_t b0, int32_t k, const void* w_packed,
+                                    int32_t npad, int32_t n, int32_t fold, float eps, float fill, void* out, int64_t out_bytes,
+                                    unsigned long long* ssq_out, unsigned long long* ssq_in, unsigned long long* ssq_zero, int32_t* row_cnt_out,
+                                    void* scratch, int64_t scratch_bytes, void* stream) {
+    const char* who = "aur_decode_proj_rows";
+    if (!ctx || !x || !w_packed || !out) return aur_fail(ctx, AUR_ERR_ARG, "%s: null argument", who);
+    if (mode != AUR_PROJ_ROW && mode != AUR_PROJ_LOGITS && mode != AUR_PROJ_SILU_MUL)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: mode %d is not AUR_PROJ_ROW, AUR_PROJ_LOGITS or AUR_PROJ_SILU_MUL", who, mode);
+    const aur_config& g = ctx->cfg;
+    if (rows < 1 || b0 < 0 || b0 + rows > g.max_batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: batch rows [%d, %d) outside [0, max_batch %d)", who, b0, b0 + rows, g.max_batch);
+    if (k < 128 || (k & 127) || k > 16384 || npad < 256 || (npad & 255) || n < 1 || n > npad)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: need k a multiple of 128 in [128, 16384], npad a positive multiple of 256, 1 <= n <= npad (got %d, %d, %d)", who, k, npad, n);
+    if (mode == AUR_PROJ_ROW && ((n & 31) || !ssq_out || fold))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: a residual projection needs n %% 32 == 0 (got %d), ssq_out, and folds no norm", who, n);
+    if (mode == AUR_PROJ_SILU_MUL && (n & 63)) return aur_fail(ctx, AUR_ERR_ARG, "%s: gate/up needs n %% 64 == 0 (got %d)", who, n);
+    if (fold && (!ssq_in || !ssq_zero)) return aur_fail(ctx, AUR_ERR_ARG, "%s: fold needs ssq_in and ssq_zero", who);
+    const int64_t rp = proj_rows_pad(ctx);
+    // out: SK_ROW the residual fp16 [rp, n]; SK_SILU_MUL fp16 [rp, n / 2]; SK_LOGITS fp32 [rp, n] + at least 4 floats of guard
+    const int64_t need = mode == AUR_PROJ_ROW ? rp * n * 2 : mode == AUR_PROJ_SILU_MUL ? rp * (n / 2) * 2 : (rp * n + 4) * 4;
+    if (out_bytes < need || ((uintptr_t)out & 15)) return aur_fail(ctx, AUR_ERR_ARG, "%s: out must be 16-byte aligned and hold %lld bytes (got %lld)", who, (long long)need, (long long)out_bytes);
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < aur_decode_proj_scratch_bytes(ctx, k, npad))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: scratch must be 256-byte aligned and hold aur_decode_proj_scratch_bytes = %lld bytes (got %lld)", who,
+                        (long long)aur_decode_proj_scratch_bytes(ctx, k, npad), (long long)scratch_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    half_t* xf = (half_t*)scratch;
+    half_t* frag = (half_t*)((char*)scratch + proj_xf_bytes(ctx, k));
+    float* part = (float*)((char*)frag + proj_frag_bytes(ctx, npad));
+    int* cnt = (int*)((char*)part + proj_part_bytes(ctx, npad));
+    // 1. producer: every batch row holds the fill, then the caller's rows land at [b0, b0 + rows)
+    const half_t fh = (half_t)fill;
+    unsigned short fbits;
+    memcpy(&fbits, &fh, 2);
+    CK(hipMemsetD16Async((hipDeviceptr_t)xf, fbits, (size_t)rp * k, s));
+    if (fold) {
+        CK(hipMemsetAsync(ssq_zero, 0x5a, (size_t)AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));       // the projection must clear all of it
+        CK(launch_xfrag_norm((const half_t*)x, k, nullptr, eps, rows, k, b0, xf, ssq_in, s));   // the prefill hand-over's call
+    } else if (b0 == 0) CK(launch_xfrag_pack((const half_t*)x, k, rows, k, xf, s));
+    else CK(launch_xfrag_norm((const half_t*)x, k, nullptr, eps, rows, k, b0, xf, nullptr, s));  // the same rows at an offset: a plain copy
+    // 2. projection
+    SkinnyArgs a{};
+    a.xf = xf; a.W = (const half_t*)w_packed; a.B = b0 + rows; a.b_lo = b0; a.b_hi = b0 + rows; a.Npad = npad; a.K = k; a.n_real = n;
+    a.mode = mode == AUR_PROJ_ROW ? SK_ROW : mode == AUR_PROJ_SILU_MUL ? SK_SILU_MUL : SK_LOGITS;
+    if (fold) { a.ssq_in = ssq_in; a.norm_eps = eps; a.ssq_zero = ssq_zero; }
+    if (a.mode == SK_ROW) {
+        CK(launch_xfrag_pack((const half_t*)out, n, (int)rp, n, frag, s));
+        CK(hipMemsetAsync(cnt, 0, (size_t)(npad / 16) * 4, s));
+        a.xres = frag; a.ssq_out = ssq_out; a.variant = ctx->skinny_variant;
+        a.part = (k >= ctx->row_split_min_k || g.max_batch > 64) ? part : nullptr;
+        a.row_cnt = ctx->fused_reduce ? cnt : nullptr; a.half_grid = ctx->decode_half;
+    } else if (a.mode == SK_SILU_MUL) {
+        CK(launch_xfrag_pack((const half_t*)out, n / 2, (int)rp, n / 2, frag, s));
+        a.out_f = frag; a.out_k32 = n / 64; a.variant = ctx->skinny_variant_wide; a.gu_ks = g.max_batch > 64 ? 1 : 2; a.half_grid = ctx->decode_half;
+    } else {
+        a.out32 = (float*)out; a.variant = ctx->skinny_variant;
+    }
+    CK(launch_skinny(a, s));
+    // 3. results back in the caller's row-major form, all round_up(max_batch, 16) batch rows
+    if (a.mode != SK_LOGITS) {
+        const int d = a.mode == SK_ROW ? n : n / 2;
+        hipLaunchKernelGGL(xfrag_unpack_kernel, dim3((unsigned)((rp * (d >> 3) + 255) / 256)), dim3(256), 0, s, frag, (int)rp, d, (half_t*)out);
+        CK(hipGetLastError());
+    }
+    if (a.mode == SK_ROW && row_cnt_out) CK(hipMemcpyAsync(row_cnt_out, cnt, (size_t)(npad / 16) * 4, hipMemcpyDeviceToDevice, s));
     return AUR_OK;
 }
 

@@ -497,14 +497,21 @@ class AuroraCapEngine:
         rm[2 * d: 3 * d] = 2 * d + np.arange(d)
         return rm
 
+    @staticmethod
+    def gateup_row_map(mlp: int, npad: int) -> np.ndarray:
+        """fused gate/up row map: packed row 2j = gate row j, 2j + 1 = up row j (row mlp + j of [gate; up]), so that one lane of the
+        SiLU*up epilogue holds both halves of h[j]"""
+        rm = np.full(npad, -1, np.int32)
+        rm[0: 2 * mlp: 2] = np.arange(mlp)
+        rm[1: 2 * mlp: 2] = mlp + np.arange(mlp)
+        return rm
+
     def _load_llm(self, w: dict):
         l = self.l
         d, H, mlp, V = l["hidden_size"], l["num_attention_heads"], l["intermediate_size"], l["vocab_size"]
         qkv_npad, gu_npad, dpad, vpad = _rup(3 * d, 256), _rup(2 * mlp, 256), _rup(d, 256), _rup(V, 256)
         rm_qkv = self.llama_qkv_row_map(d, H, qkv_npad)
-        rm_gu = np.full(gu_npad, -1, np.int32)
-        rm_gu[0: 2 * mlp: 2] = np.arange(mlp)
-        rm_gu[1: 2 * mlp: 2] = mlp + np.arange(mlp)
+        rm_gu = self.gateup_row_map(mlp, gu_npad)
         # RMSNorm weights are FOLDED into the projection that consumes the normalised activations:
         #   W (w_norm * x_hat) = (W diag(w_norm)) x_hat.  The kernels then only need the per-row 1/rms
         #   (prefill: weight-less norm kernel; decode: sum(x^2) carried by the residual-producing epilogues).
@@ -1566,6 +1573,31 @@ class AuroraCapEngine:
                                                     self._stream()), "aur_attn_decode_rows")
         torch.cuda.synchronize()
         return out
+
+    PROJ_MODES = {"row": 0, "logits": 1, "silu_mul": 2}
+
+    def decode_proj_rows(self, mode: str, x: torch.Tensor, w_packed: torch.Tensor, n: int, out: torch.Tensor, *, b0: int = 0, fold: bool = False,
+                         eps: float = 1e-5, fill: float = 0.0, ssq_out: Optional[torch.Tensor] = None, ssq_in: Optional[torch.Tensor] = None) -> dict:
+        """aur_decode_proj_rows: one decode projection ("row", "silu_mul", "logits") on caller rows x [rows, k] at batch rows [b0, b0 + rows).
+        `out` is the initial content of the output for all round_up(max_batch, 16) batch rows: the residual fp16 [rp, n] ("row"), the
+        sentinel fp16 [rp, n / 2] ("silu_mul"), or fp32 [rp * n + guard] ("logits").  ssq_out / ssq_in: initial int64 [16, 128] arrays.
+        Returns dict(out, ssq_out, ssq_in, ssq_zero, row_cnt) of device tensors as they are after the launch (None where unused)."""
+        xh = self._h(x)
+        rows, k = xh.shape
+        npad = w_packed.numel() // k
+        o = out.detach().to(self.dev).contiguous().clone()
+        zeros = lambda: torch.zeros(16, 128, dtype=torch.int64, device=self.dev)
+        so = ssq_out.to(self.dev).contiguous().clone() if ssq_out is not None else (zeros() if mode == "row" else None)
+        si = (ssq_in.to(self.dev).contiguous().clone() if ssq_in is not None else zeros()) if fold else None
+        sz = zeros() if fold else None
+        cnt = torch.full((npad // 16,), -1, dtype=torch.int32, device=self.dev) if mode == "row" else None
+        scratch = torch.empty(self.L.aur_decode_proj_scratch_bytes(self.ctx, k, npad), dtype=torch.uint8, device=self.dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        check(self.ctx, self.L.aur_decode_proj_rows(self.ctx, self.PROJ_MODES[mode], xh.data_ptr(), rows, b0, k, w_packed.data_ptr(), npad, n,
+                                                    int(fold), eps, fill, o.data_ptr(), o.numel() * o.element_size(), ptr(so), ptr(si), ptr(sz),
+                                                    ptr(cnt), scratch.data_ptr(), scratch.numel(), self._stream()), "aur_decode_proj_rows")
+        torch.cuda.synchronize()
+        return dict(out=o, ssq_out=so, ssq_in=si, ssq_zero=sz, row_cnt=cnt)
 
     def set_option(self, name: str, value: int):
         check(self.ctx, self.L.aur_set_option(self.ctx, name.encode(), int(value)), "aur_set_option")

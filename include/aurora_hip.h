@@ -282,7 +282,7 @@ int aur_tome_step(aur_ctx* ctx, const float* metric, const void* x, const float*
  * (npad % 128 == 0, K % 64 == 0); bias fp32 [npad] or NULL; act 0 / AUR_ACT_*; resid fp16 [M, n] or NULL. */
 int aur_linear(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                int32_t n, const float* bias, int32_t act, const void* resid, void* c, void* stream);
-/* Same contraction through the decode (m <= 64) weight-streaming kernel; out fp32 [m, n]. */
+/* Same contraction through the decode weight-streaming kernel (m <= 128, k % 128 == 0, any n <= npad); out fp32 [m, n]. */
 int aur_linear_skinny(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                       int32_t n, float* out, void* stream);
 int aur_layernorm(aur_ctx* ctx, const void* x, int32_t rows, int32_t d, const float* w, const float* b,
@@ -321,6 +321,27 @@ int aur_attn_rows(aur_ctx* ctx, int32_t layout, const void* x, int32_t nseq, int
 int64_t aur_attn_decode_scratch_bytes(const aur_ctx* ctx, int32_t kx);
 int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, const void* w_packed, int32_t npad, const int32_t* pos_dev,
                          int32_t rope, void* scratch, int64_t scratch_bytes, void* out, void* stream);
+
+/* One decode projection alone on caller rows (tests/test_gpu_skinny_modes.py): the producer of x fragments, then launch_skinny in the
+ * structure the decode step of THIS engine picks (capacity, "skinny_row_split_min_k", "decode_fused_reduce", "decode_half_grid").
+ * x fp16 [rows, k] lands at batch rows [b0, b0 + rows) (b0 + rows <= max_batch; k % 128 == 0); every other batch row of the x fragments,
+ * up to rp = round_up(max_batch, 16), holds `fill`.  fold = 1: the producer is the prefill hand-over's (x fragments + sum(x^2) into
+ * ssq_in), the projection scales by rsqrt(sum / k + eps) and must clear ssq_zero, which the entry fills with a non-zero pattern first;
+ * fold = 0: plain fragments.  w_packed [npad, k] from aur_pack_linear (npad % 256 == 0; AUR_PROJ_SILU_MUL: gate / up rows interleaved).
+ * mode AUR_PROJ_ROW      (no fold, n % 32 == 0): out fp16 [rp, n] is the residual, in and out; ssq_out u64 [16][128] in and out (the
+ *                        projection adds); row_cnt_out int32 [npad / 16] or NULL: the fused reduce's arrival counters after the launch.
+ *      AUR_PROJ_SILU_MUL (n % 64 == 0): out fp16 [rp, n / 2], in (the caller's sentinel) and out.
+ *      AUR_PROJ_LOGITS   (any n): out fp32 [rp, n] plus at least 4 floats of guard, written in place (16-byte aligned).
+ * out_bytes: size of out.  ssq_in / ssq_zero: u64 [16][128] device arrays (fold only).  scratch: 256-byte aligned, at least
+ * aur_decode_proj_scratch_bytes bytes; no workspace buffer is used.  Bad arguments: AUR_ERR_ARG, the ctx stays usable. */
+#define AUR_PROJ_ROW 0
+#define AUR_PROJ_LOGITS 1
+#define AUR_PROJ_SILU_MUL 2
+int64_t aur_decode_proj_scratch_bytes(const aur_ctx* ctx, int32_t k, int32_t npad);
+int aur_decode_proj_rows(aur_ctx* ctx, int32_t mode, const void* x, int32_t rows, int32_t b0, int32_t k, const void* w_packed, int32_t npad,
+                         int32_t n, int32_t fold, float eps, float fill, void* out, int64_t out_bytes, unsigned long long* ssq_out,
+                         unsigned long long* ssq_in, unsigned long long* ssq_zero, int32_t* row_cnt_out, void* scratch,
+                         int64_t scratch_bytes, void* stream);
 
 /* Copy the last-position logits of the most recent prefill / decode step into dst_dev: fp32 [batch, vocab]. */
 int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);

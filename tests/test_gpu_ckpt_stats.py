@@ -23,7 +23,7 @@ from oracle import aurora_oracle as O
 from oracle import tome_ref
 from tests.test_gpu_llm import LLM_CFGS, LLM_CFGS_VOCAB, padded
 from tests.util import (CKPT_LLM_CFG, CKPT_NEW_TOKENS, CKPT_VIT_CASES, ckpt_like_llm_case, ckpt_like_vit_input, ckpt_like_vit_weights,
-                        ckpt_llm_cases, golden, observe, rand_llm_weights, rel_l2, to_match, tt)
+                        ckpt_llm_cases, gemm_bound, golden, observe, outlier_operands, rand_llm_weights, rel_l2, to_match, tt)
 
 pytestmark = pytest.mark.gpu
 
@@ -357,24 +357,6 @@ def test_norm_kernels_against_fp64_with_derived_bounds(keng, rows, d):
     for i, k in enumerate(kinds):
         if k == "zero":
             assert not out[i].any()
-
-
-def outlier_operands(m, n, k, g):
-    """A with one column x 1000, W with 0.1 % of its entries x 20 (fp16-representable)"""
-    a = torch.randn(m, k, generator=g) * 0.5
-    a[:, int(torch.randint(0, k, (1,), generator=g))] *= 1000.0
-    w = torch.randn(n, k, generator=g) * 0.05
-    hit = torch.randperm(n * k, generator=g)[: max(1, n * k // 1000)]
-    w.view(-1)[hit] *= 20.0
-    return a.half(), w.half()
-
-
-def gemm_bound(a, w, ref, fp16_out):
-    """2^-11 |ref| (the fp16 output rounding; none for an fp32 output) + K 2^-24 sum_k |a_k| |w_k| (fp32 accumulation, worst case: the
-    fp16 x fp16 products are exact in fp32, each of the K additions rounds by at most 2^-24 of a partial sum <= sum |a| |w|)"""
-    k = a.shape[1]
-    acc = k * 2.0 ** -24 * (a.double().abs() @ w.double().abs().T)
-    return acc + (2.0 ** -11 * ref.abs() if fp16_out else 0.0)
 
 
 @pytest.mark.parametrize("m,n,k", [(77, 256, 1280), (2142, 512, 4096)])

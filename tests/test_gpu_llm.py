@@ -97,6 +97,38 @@ def test_prefill_and_stepwise_decode_logits(name, L):
         eng.close()
 
 
+def test_odd_vocabulary_logits_in_a_batch():
+    """v323 (rows of logits end off the 16-byte grid) with three slots decoding together: every slot's logits - column 0 included, the
+    address right behind the previous row's last column - against the oracle, and bitwise those of the slot decoded alone"""
+    cfg = LLM_CFGS_VOCAB["v323"]
+    lens, nnew = (40, 97, 33), 6
+    gen = torch.Generator().manual_seed(11)
+    embs = [torch.randn(L, cfg["hidden_size"], generator=gen).half().float() for L in lens]
+
+    def stepwise(eng, which):
+        eng.begin_batch(len(which), nnew, None)
+        for slot, i in enumerate(which):
+            eng.prefill(slot, padded(embs[i]), lens[i])
+        logits = [eng.logits().cpu()]
+        for _ in range(nnew - 1):
+            eng.decode(1)
+            logits.append(eng.logits().cpu())
+        return torch.stack(logits, 1), eng.outputs()              # [slot, step, vocab]
+
+    eng, w = make_engine(cfg, 5, max_batch=3, use_graph=False)
+    try:
+        together, ids = stepwise(eng, (0, 1, 2))
+        for i in range(3):
+            alone, ids1 = stepwise(eng, (i,))
+            assert ids1[0] == ids[i]
+            assert torch.equal(alone[0], together[i]), ("a slot's logits depend on its neighbours", i)
+            ref = teacher_forced_logits(embs[i], ids[i], w, cfg)
+            scale = ref.abs().max().item()
+            observe("llm/odd_vocab_batched_logits_max_err_over_scale", (together[i] - ref).abs().max().item() / scale, LOGIT_TOL)
+    finally:
+        eng.close()
+
+
 def test_greedy_matches_oracle_ids_and_graph_equals_eager():
     cfg = LLM_CFGS["hd128"]
     emb = torch.randn(50, cfg["hidden_size"], generator=torch.Generator().manual_seed(3)).half().float()

@@ -274,6 +274,25 @@ def to_match(idx: dict, device="cpu"):
 _OBSERVED = {}
 
 
+# ---- GEMM operands with outliers and the elementwise bound of an fp32-accumulating GEMM (test_gpu_ckpt_stats.py, skinny_ref.py)
+def outlier_operands(m, n, k, g):
+    """A with one column x 1000, W with 0.1 % of its entries x 20 (fp16-representable)"""
+    a = torch.randn(m, k, generator=g) * 0.5
+    a[:, int(torch.randint(0, k, (1,), generator=g))] *= 1000.0
+    w = torch.randn(n, k, generator=g) * 0.05
+    hit = torch.randperm(n * k, generator=g)[: max(1, n * k // 1000)]
+    w.view(-1)[hit] *= 20.0
+    return a.half(), w.half()
+
+
+def gemm_bound(a, w, ref, fp16_out):
+    """2^-11 |ref| (the fp16 output rounding; none for an fp32 output) + K 2^-24 sum_k |a_k| |w_k| (fp32 accumulation, worst case: the
+    fp16 x fp16 products are exact in fp32, each of the K additions rounds by at most 2^-24 of a partial sum <= sum |a| |w|)"""
+    k = a.shape[1]
+    acc = k * 2.0 ** -24 * (a.double().abs() @ w.double().abs().T)
+    return acc + (2.0 ** -11 * ref.abs() if fp16_out else 0.0)
+
+
 def observe(key, value, bound, at_least=False):
     """assert value <= bound (or >= bound with at_least) - `bound` is the shared constant; the comparison's own entry in
     tests/parity_bounds.PER_COMPARISON wins when it is tighter - and remember the worst value seen under `key`"""
