@@ -96,6 +96,11 @@ struct aur_ctx {
         int32_t *s_pos, *s_ids, *s_len, *s_fin;
         aur_sampling* s_samp;                                // per-slot sampling parameters (aur_slot_sampling); temperature 0 = greedy
         int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
+        // log-probabilities of generated tokens (aur_logprob_enable): the caller's buffer, nullptr = off.  lp_len [max_batch]: tokens of
+        // slot b recorded so far; lp [b][max_new], lp_top_id / lp_top_lp [b][max_new][lp_top_n]: rows max_new apart, like s_ids
+        int32_t *lp_len = nullptr, *lp_top_id = nullptr;
+        float *lp = nullptr, *lp_top_lp = nullptr;
+        int lp_top_n = 0;
         int batch = 0, max_new = 0, eos = -1;
         hipGraphExec_t graph = nullptr, graph_h = nullptr;   // decode step: full grid / half grid (decode_half)
         int graph_batch = 0;
@@ -937,6 +942,12 @@ static KvLayout llm_kv(const aur_ctx* c, int layer) {
     return L;
 }
 
+// slots [b0, b0 + nb) of bank K hold no log-probability record: wherever their s_len is zeroed
+static int logprob_clear(aur_ctx* ctx, const aur_ctx::Bank& K, int b0, int nb, hipStream_t s) {
+    if (K.lp_len) CK(launch_token_logprob_clear(b0, nb, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id, K.lp_top_lp, s));
+    return AUR_OK;
+}
+
 extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_tokens, int32_t eos_id, void* stream) {
     NO_CAPTURE("aur_begin_batch");
     if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_begin_batch: language weights not finalized");
@@ -960,7 +971,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
     CK(hipMemsetAsync(K.s_ssq_mlp, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
     CK(hipMemsetAsync(K.s_ssq_attn, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
-    return AUR_OK;
+    return logprob_clear(ctx, K, 0, g.max_batch, s);
 }
 
 // logits for batch columns [b0, b0 + nb) from the residual rows in d_x (x-fragment form; final RMSNorm folded into the
@@ -980,6 +991,10 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     else
         CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
                                  K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
+    // the log-probability of what was just picked, under the row it was picked from: a launch of its own behind the pick, which stays as it is
+    if (K.lp_len)
+        CK(launch_token_logprob(K.d_logits, b0, nb, g.llm_vocab, K.s_ids, K.s_len, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id,
+                                K.lp_top_lp, s));
     return AUR_OK;
 }
 
@@ -1205,6 +1220,7 @@ static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq
     CK(hipMemsetAsync(K.s_fin + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
+    if (int rc = logprob_clear(ctx, K, slot0, nseq, s)) return rc;
     return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit", lens, pos0);
 }
 extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
@@ -1817,7 +1833,7 @@ extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     CK(hipMemsetAsync(K.s_fin + slot, 0, 4, s));
     CK(hipMemsetAsync(K.s_pos + slot, 0, 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
-    return AUR_OK;
+    return logprob_clear(ctx, K, slot, 1, s);
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
     if (int rc = slot_check(ctx, slot, "aur_slot_retire")) return rc;
@@ -1841,6 +1857,82 @@ extern "C" int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int
     hipStream_t s = (hipStream_t)stream;
     CK(hipMemcpyAsync(ids_dev, K.s_ids + (int64_t)slot0 * K.max_new, (size_t)nslots * K.max_new * 4, hipMemcpyDeviceToDevice, s));
     CK(hipMemcpyAsync(lens_dev, K.s_len + slot0, (size_t)nslots * 4, hipMemcpyDeviceToDevice, s));
+    return AUR_OK;
+}
+// ---- log-probabilities of generated tokens
+static int64_t logprob_entries(const aur_config& g) { return (int64_t)g.max_batch * g.max_new_tokens; }
+extern "C" int64_t aur_logprob_bytes(const aur_ctx* ctx, int32_t top_n) {
+    if (!ctx || top_n < 0 || top_n > 8) return -1;
+    return 4 * ((int64_t)ctx->cfg.max_batch + logprob_entries(ctx->cfg) * (1 + 2 * (int64_t)top_n));
+}
+extern "C" int aur_logprob_enable(aur_ctx* ctx, int32_t top_n, void* buf_dev, int64_t nbytes, void* stream) {
+    NO_CAPTURE("aur_logprob_enable");
+    aur_ctx::Bank& K = ctx->bank();
+    if (buf_dev) {
+        if (top_n < 0 || top_n > 8) return aur_fail(ctx, AUR_ERR_ARG, "aur_logprob_enable: top_n %d outside [0, 8]", top_n);
+        if (((uintptr_t)buf_dev & 15) || nbytes < aur_logprob_bytes(ctx, top_n))
+            return aur_fail(ctx, AUR_ERR_ARG, "aur_logprob_enable: buffer of %lld bytes (need %lld, 16-byte aligned)", (long long)nbytes,
+                            (long long)aur_logprob_bytes(ctx, top_n));
+    }
+    // whether the step launches token_logprob_kernel, and with which pointers, is frozen inside this bank's captured decode graphs
+    if (K.graph || K.graph_h) {
+        (void)hipDeviceSynchronize();
+        drop_graphs(K);
+    }
+    K.lp_len = nullptr;
+    if (!buf_dev) return AUR_OK;
+    const aur_config& g = ctx->cfg;
+    const int64_t n = logprob_entries(g);
+    int32_t* len = (int32_t*)buf_dev;
+    float* lp = (float*)(len + g.max_batch);
+    int32_t* tid = (int32_t*)(lp + n);
+    float* tlp = (float*)(tid + n * top_n);
+    // every slot without a record, at the widest row distance: that is every entry of the buffer, whatever max_new a batch runs with
+    CK(launch_token_logprob_clear(0, g.max_batch, g.max_new_tokens, top_n, len, lp, tid, tlp, (hipStream_t)stream));
+    K.lp_len = len; K.lp = lp; K.lp_top_id = tid; K.lp_top_lp = tlp; K.lp_top_n = top_n;
+    return AUR_OK;
+}
+// counterpart of aur_get_outputs: synchronises.  lp_host [batch * max_new_tokens], top_ids_host / top_lp_host [batch * max_new_tokens * top_n]
+// (may be NULL), lens_host [batch]: tokens recorded per slot.
+extern "C" int aur_get_logprobs(aur_ctx* ctx, float* lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* lens_host, void* stream) {
+    NO_CAPTURE("aur_get_logprobs");
+    hipStream_t s = (hipStream_t)stream;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.lp_len || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_get_logprobs: not enabled on this bank (aur_logprob_enable), or no active batch");
+    const size_t n = (size_t)K.batch * K.max_new;
+    if (lp_host) CK(hipMemcpyAsync(lp_host, K.lp, n * 4, hipMemcpyDeviceToHost, s));
+    if (top_ids_host && K.lp_top_n) CK(hipMemcpyAsync(top_ids_host, K.lp_top_id, n * K.lp_top_n * 4, hipMemcpyDeviceToHost, s));
+    if (top_lp_host && K.lp_top_n) CK(hipMemcpyAsync(top_lp_host, K.lp_top_lp, n * K.lp_top_n * 4, hipMemcpyDeviceToHost, s));
+    if (lens_host) CK(hipMemcpyAsync(lens_host, K.lp_len, (size_t)K.batch * 4, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    return AUR_OK;
+}
+// counterpart of aur_slot_collect: device-to-device, enqueue-only, recordable
+extern "C" int aur_slot_collect_logprobs(aur_ctx* ctx, int32_t slot0, int32_t nslots, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev,
+                                         int32_t* lens_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_collect_logprobs")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.lp_len) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_collect_logprobs: not enabled on this bank (aur_logprob_enable)");
+    if (nslots < 1 || slot0 + nslots > K.batch || !lp_dev || !lens_dev || (K.lp_top_n && (!top_ids_dev || !top_lp_dev)))
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_collect_logprobs: slots [%d, %d) outside the batch of %d, or a null output", slot0, slot0 + nslots, K.batch);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t e0 = (int64_t)slot0 * K.max_new;
+    const size_t n = (size_t)nslots * K.max_new;
+    CK(hipMemcpyAsync(lp_dev, K.lp + e0, n * 4, hipMemcpyDeviceToDevice, s));
+    if (K.lp_top_n) {
+        CK(hipMemcpyAsync(top_ids_dev, K.lp_top_id + e0 * K.lp_top_n, n * K.lp_top_n * 4, hipMemcpyDeviceToDevice, s));
+        CK(hipMemcpyAsync(top_lp_dev, K.lp_top_lp + e0 * K.lp_top_n, n * K.lp_top_n * 4, hipMemcpyDeviceToDevice, s));
+    }
+    CK(hipMemcpyAsync(lens_dev, K.lp_len + slot0, (size_t)nslots * 4, hipMemcpyDeviceToDevice, s));
+    return AUR_OK;
+}
+extern "C" int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* tokens_dev, int32_t top_n,
+                                      float* lp_out, int32_t* top_ids_out, float* top_lp_out, void* stream) {
+    if (!ctx || !logits || !tokens_dev || !lp_out) return aur_fail(ctx, AUR_ERR_ARG, "aur_token_logprob_rows: null argument");
+    if (rows < 1 || vocab < 1) return aur_fail(ctx, AUR_ERR_ARG, "aur_token_logprob_rows: rows %d or vocab %d < 1", rows, vocab);
+    if (top_n < 0 || top_n > 8 || (top_n && (!top_ids_out || !top_lp_out)))
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_token_logprob_rows: top_n %d outside [0, 8], or null outputs for it", top_n);
+    CK(launch_token_logprob_rows(logits, rows, vocab, tokens_dev, top_n, lp_out, top_ids_out, top_lp_out, (hipStream_t)stream));
     return AUR_OK;
 }
 extern "C" int aur_slot_sampling(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_sampling* params_dev, void* stream) {

@@ -220,6 +220,16 @@ hipError_t launch_sample_rows(const float* logits, int rows, int vocab, const au
 // any rows of a prefill pass to the pick path's lm_head (aur_llm_score_var)
 hipError_t launch_score_rows(const float* logits, int rows, int vocab, const int32_t* targets, float* logprob_out, int32_t* argmax_out,
                              hipStream_t s);
+// log-probabilities of generated tokens (top_n <= 8 alternatives each).  launch_token_logprob runs BEHIND the pick over slots
+// [b0, b0 + nb): a slot whose out_len differs from lp_len gets the record of its newest token at index out_len - 1 of lp [.., max_new],
+// top_id / top_lp [.., max_new, top_n], and lp_len = out_len.  _rows: the same evaluation on caller rows, one token per row.  _clear:
+// slots [b0, b0 + nb) hold no record (lp_len 0, lp 0, ranks (-1, 0.0)).
+hipError_t launch_token_logprob(const float* logits, int b0, int nb, int vocab, const int32_t* out_ids, const int32_t* out_len, int max_new,
+                                int top_n, int32_t* lp_len, float* lp, int32_t* top_id, float* top_lp, hipStream_t s);
+hipError_t launch_token_logprob_rows(const float* logits, int rows, int vocab, const int32_t* tokens, int top_n, float* lp, int32_t* top_id,
+                                     float* top_lp, hipStream_t s);
+hipError_t launch_token_logprob_clear(int b0, int nb, int max_new, int top_n, int32_t* lp_len, float* lp, int32_t* top_id, float* top_lp,
+                                      hipStream_t s);
 // column b < n of xf = flat row rows[b] of x (sequence rows[b] / stride, row rows[b] % stride) + its sum(x^2); entries that are negative,
 // outside nseq * stride or at / beyond their sequence's clamped length - and columns [n, ncols) - are zero rows; eff_targets[b] =
 // targets[b] for a live entry, -1 otherwise

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from . import sampling as S
+from .scoring import check_logprobs
 from ._lib import AurConfig, check
 
 IMAGE_TOKEN_INDEX = -200     # src/xtuner/xtuner/utils/constants.py:4
@@ -334,6 +335,8 @@ class AuroraCapEngine:
         self._bank = 0
         self._sampling_mode = False                      # ctx option "sampling": flipped by the first sampling request, sticky
         self._samp_stage = None                          # device staging of aur_sampling records, one row per (bank, slot)
+        self._lp_bufs: Dict[int, torch.Tensor] = {}      # bank -> the caller-owned state of aur_logprob_enable (kept once allocated)
+        self._lp_top: Dict[int, int] = {}                # bank -> top_n it records with; absent = off
         self.c = c
         self.v, self.l = v, l
         self.max_new_tokens = max_new_tokens
@@ -744,12 +747,22 @@ class AuroraCapEngine:
     def decode(self, steps: int):
         check(self.ctx, self.L.aur_llm_decode(self.ctx, steps, self._stream()), "aur_llm_decode")
 
-    def outputs(self):
+    def outputs(self, logprobs: Optional[int] = None):
+        """The generated ids of every slot; with logprobs=n (a bank that records them, `_logprobs_on`) a dict per slot instead:
+        ids, token_logprobs float32 [len], top_ids int32 [len, n], top_logprobs float32 [len, n]."""
         ids = np.zeros((self._batch, self._max_new), np.int32)
         lens = np.zeros(self._batch, np.int32)
         check(self.ctx, self.L.aur_get_outputs(self.ctx, ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                                lens.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "aur_get_outputs")
-        return [ids[b, : lens[b]].tolist() for b in range(self._batch)]
+        out = [ids[b, : lens[b]].tolist() for b in range(self._batch)]
+        if logprobs is None:
+            return out
+        n = check_logprobs(logprobs)
+        rec, lp, tid, tlp = self.token_logprob_state()
+        if (rec != lens).any():
+            raise RuntimeError(f"log-probability records {rec.tolist()} for generated lengths {lens.tolist()}: enabled in mid-generation?")
+        return [dict(ids=out[b], token_logprobs=lp[b, :lens[b]].copy(), top_ids=tid[b, :lens[b], :n].copy(),
+                     top_logprobs=tlp[b, :lens[b], :n].copy()) for b in range(self._batch)]
 
     def unfinished(self) -> int:
         n = C.c_int32(0)
@@ -904,6 +917,74 @@ class AuroraCapEngine:
                     results[chunk[m][0]] = dict(logprob=total, greedy=greedy, token_logprobs=lps, count=n)
         return results
 
+    # ------------------------------------------------------------------ log-probabilities of generated tokens
+    def _logprobs_on(self, n: int):
+        """The current bank records the log-probability of every token it generates from now on, with at least `n` alternatives
+        (`scoring.token_logprobs`): one more launch behind every pick.  The state is a buffer this engine allocates per bank on first
+        use; the bank's decode graphs are re-captured once.  Sticky, like `_sampling_on`: later calls without logprobs= keep
+        recording (`logprobs_off` ends it).  A process that never asks never gets here."""
+        cur = self._lp_top.get(self._bank)
+        if cur is not None and cur >= n:
+            return                                                # the first n of more ranks are the n ranks: same rounds, same bits
+        nbytes = int(self.L.aur_logprob_bytes(self.ctx, n))
+        buf = self._lp_bufs.get(self._bank)
+        if buf is None or buf.numel() < nbytes:
+            torch.cuda.synchronize(self.dev)                      # queued steps may still write the buffer this one replaces
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        check(self.ctx, self.L.aur_logprob_enable(self.ctx, n, buf.data_ptr(), nbytes, self._stream()), "aur_logprob_enable")
+        self._lp_bufs[self._bank], self._lp_top[self._bank] = buf, n
+
+    def logprobs_off(self):
+        """No bank records log-probabilities any more: the launches are those of an engine that never asked (the buffers are kept
+        for the next request)."""
+        bank = self._bank
+        for b in sorted(self._lp_top):
+            self.select_bank(b)
+            check(self.ctx, self.L.aur_logprob_enable(self.ctx, 0, None, 0, self._stream()), "aur_logprob_enable")
+            del self._lp_top[b]
+        self.select_bank(bank)
+
+    def token_logprob_state(self):
+        """The current bank's records as numpy (synchronises): lens int32 [batch], token log-probabilities float32 [batch, max_new],
+        top ids int32 / top log-probabilities float32 [batch, max_new, top_n].  Entries at or beyond a slot's length are 0 / (-1, 0)."""
+        top = self._lp_top[self._bank]
+        B, M = self._batch, self._max_new
+        lens, lp = np.zeros(B, np.int32), np.zeros((B, M), np.float32)
+        tid, tlp = np.zeros((B, M, top), np.int32), np.zeros((B, M, top), np.float32)
+        check(self.ctx, self.L.aur_get_logprobs(self.ctx, lp.ctypes.data_as(C.c_void_p), tid.ctypes.data_as(C.c_void_p),
+                                                tlp.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), self._stream()),
+              "aur_get_logprobs")
+        return lens, lp, tid, tlp
+
+    def slot_collect_logprobs(self, slot0: int, nslots: int, lp_dev: torch.Tensor, top_ids_dev: torch.Tensor, top_lp_dev: torch.Tensor,
+                              lens_dev: torch.Tensor):
+        """Async device copy of the records of slots [slot0, slot0 + nslots) (`slot_collect`'s counterpart): lp_dev float32
+        [nslots, max_new], top_ids_dev int32 / top_lp_dev float32 [nslots, max_new, top_n of the bank], lens_dev int32 [nslots]."""
+        top = self._lp_top[self._bank]
+        n = nslots * self._max_new
+        assert lp_dev.dtype == torch.float32 and top_lp_dev.dtype == torch.float32 and top_ids_dev.dtype == torch.int32 and lens_dev.dtype == torch.int32
+        assert all(t.is_cuda and t.is_contiguous() for t in (lp_dev, top_ids_dev, top_lp_dev, lens_dev))
+        assert lp_dev.numel() >= n and top_ids_dev.numel() >= n * top and top_lp_dev.numel() >= n * top and lens_dev.numel() >= nslots
+        check(self.ctx, self.L.aur_slot_collect_logprobs(self.ctx, slot0, nslots, lp_dev.data_ptr(), top_ids_dev.data_ptr(), top_lp_dev.data_ptr(),
+                                                         lens_dev.data_ptr(), self._stream()), "aur_slot_collect_logprobs")
+
+    def token_logprob_rows(self, logits: torch.Tensor, tokens, top_n: int = 0):
+        """The kernel alone (aur_token_logprob_rows): logits fp32 [rows, vocab] on the device, one token per row (a list, or an int32
+        device tensor) -> (log-probabilities float32 [rows], top ids int32 [rows, top_n], their log-probabilities float32
+        [rows, top_n]) as numpy.  A token outside [0, vocab): (0, -1 .., 0 ..)."""
+        top_n = check_logprobs(top_n)
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) == logits.shape[1]
+        rows, vocab = logits.shape
+        tg = tokens if torch.is_tensor(tokens) else torch.tensor([int(t) for t in tokens], dtype=torch.int32, device=self.dev)
+        assert tg.dtype == torch.int32 and tg.is_cuda and tg.numel() >= rows
+        lp = torch.empty(rows, dtype=torch.float32, device=self.dev)
+        tid = torch.empty(rows, max(top_n, 1), dtype=torch.int32, device=self.dev)
+        tlp = torch.empty(rows, max(top_n, 1), dtype=torch.float32, device=self.dev)
+        check(self.ctx, self.L.aur_token_logprob_rows(self.ctx, logits.data_ptr(), rows, vocab, tg.data_ptr(), top_n, lp.data_ptr(),
+                                                      tid.data_ptr(), tlp.data_ptr(), self._stream()), "aur_token_logprob_rows")
+        torch.cuda.synchronize()
+        return lp.cpu().numpy(), tid.cpu().numpy()[:, :top_n], tlp.cpu().numpy()[:, :top_n]
+
     # ------------------------------------------------------------------ sampling
     def _sampling_on(self):
         """The first sampling request switches the ctx's token pick to sample_advance_kernel (decode graphs are re-captured once);
@@ -952,14 +1033,20 @@ class AuroraCapEngine:
         return tok.cpu().numpy(), kept.cpu().numpy()
 
     def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
-                 sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None):
+                 sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None):
         """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
         sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
-        the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours."""
+        the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours.
+        logprobs=n (0 .. 8): each result is a dict - ids, token_logprobs float32 [len], top_ids int32 [len, n], top_logprobs float32
+        [len, n] - as `scoring.token_logprobs` defines them: under the model's unmodified distribution, whatever `sampling` says;
+        the ids are the same.  None: the list of ids, and no extra work."""
+        lpn = check_logprobs(logprobs)
         B = len(embeds_list)
         samp = S.check_sampling(sampling)
         if samp is not None:
             self._sampling_on()
+        if lpn is not None:
+            self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         for b in range(B):
@@ -971,19 +1058,20 @@ class AuroraCapEngine:
             done += n
             if eos_id is not None and self.unfinished() == 0:
                 break
-        return self.outputs()
+        return self.outputs(lpn)
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
-                    eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0) -> List[int]:
-        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream: as in `generate`."""
+                    eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None):
+        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs: as in `generate`."""
+        check_logprobs(logprobs)
         r = self.tome_r(token_kept_ratio, pixels.shape[-2], pixels.shape[-1])
         vis = self.vit_encode(pixels, r)
         emb, L = self.project_splice(vis, input_ids)
-        return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream])[0]
+        return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream], logprobs=logprobs)[0]
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
-                      streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None) -> List[List[int]]:
+                      streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None):
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
@@ -994,7 +1082,9 @@ class AuroraCapEngine:
         is spliced over the first clip's kept visual rows -, takes the whole KV pages the two prompts have in common from the first
         clip's slot (`kv_copy_prefix`) and prefills only its remaining rows, neighbouring siblings in one pass (`extend_batch`).  A
         sibling whose prompt shares less than a page with the first clip's, or diverges from it before the visual rows end, takes the
-        unshared path.  The same ids either way; share=None is exactly the path above."""
+        unshared path.  The same ids either way; share=None is exactly the path above.
+        logprobs=n: a dict per clip instead of its ids, as in `generate`."""
+        lpn = check_logprobs(logprobs)
         B = len(clips)
         samp = S.check_sampling(sampling)
         if not 1 <= B <= self.max_batch:
@@ -1022,6 +1112,8 @@ class AuroraCapEngine:
         vis_of = {}
         if samp is not None:
             self._sampling_on()
+        if lpn is not None:
+            self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         runs, b0 = [], 0                                          # maximal runs of neighbouring clips that are nobody's sibling
@@ -1068,19 +1160,22 @@ class AuroraCapEngine:
             done += n
             if eos_id is not None and self.unfinished() == 0:
                 break
-        return self.outputs()
+        return self.outputs(lpn)
 
     def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
-                        eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+                        eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None,
+                        logprobs: Optional[int] = None):
         """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
-        (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives."""
+        (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs: as in `generate`."""
+        check_logprobs(logprobs)
         prompts = [list(ids) for ids in list_of_input_ids]
         st = list(range(len(prompts))) if streams is None else [int(x) for x in streams]
         out: List[List[int]] = []
         for c0 in range(0, len(prompts), self.max_batch):
             chunk = prompts[c0:c0 + self.max_batch]
             out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
-                                      streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk))
+                                      streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk),
+                                      **({} if logprobs is None else dict(logprobs=logprobs)))
         return out
 
     # ------------------------------------------------------------------ continuous batching
@@ -1106,7 +1201,7 @@ class AuroraCapEngine:
 
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
-                       sampling: Optional[dict] = None, stream_of=None, share_key=None):
+                       sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -1129,10 +1224,15 @@ class AuroraCapEngine:
         spliced over the kept visual rows, and a prefill of the rows behind the fork only (`share_fork`; a clip that cannot fork takes
         the normal path).  In the overlapped mode such a front end runs eagerly on the front-end stream (never from a captured graph).
         Same ids either way.  An engine whose only spare sequences are holders must be called with overlap=False: the default
-        follows spare_slots."""
+        follows spare_slots.
+        logprobs=n: yields (index, dict) - ids, token_logprobs, top_ids, top_logprobs as in `generate` - in both modes, for clips
+        from either front end."""
+        lpn = check_logprobs(logprobs)
         samp = S.check_sampling(sampling)
         if samp is not None:
             self._sampling_on()
+        if lpn is not None:
+            self._logprobs_on(lpn)
         B = self.max_batch if slots is None else slots
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"slots={B} for an engine built with max_batch={self.max_batch}")
@@ -1146,7 +1246,7 @@ class AuroraCapEngine:
             if self.spare_slots - n_hold < 1:
                 raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1 beyond its prefix_cache")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph, samp, stream_of, share_key, holders)
+                                                       front_graph, samp, stream_of, share_key, holders, lpn)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -1195,7 +1295,7 @@ class AuroraCapEngine:
             lens, fin = self.slot_state()
             done = [s for s in range(B) if owner[s] is not None and fin[s]]
             if done:
-                out = self.outputs()
+                out = self.outputs(lpn)
                 for s in done:
                     yield owner[s], out[s]
                     owner[s] = None
@@ -1293,7 +1393,7 @@ class AuroraCapEngine:
         return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"]), fg
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
-                                   samp=None, stream_of=None, share_key=None, holders=None):
+                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -1405,7 +1505,7 @@ class AuroraCapEngine:
                 lens, fin = self.slot_state()
                 done = [s for s in range(B) if owner[s] is not None and fin[s]]
                 if done:
-                    out = self.outputs()
+                    out = self.outputs(lpn)
                     for s in done:
                         yield owner[s], out[s]
                         owner[s] = None

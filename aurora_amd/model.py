@@ -20,6 +20,7 @@ import torch
 
 from .engine import AuroraCapEngine
 from .sampling import DEFAULT_TOP_K, check_sampling
+from .scoring import check_logprobs
 
 DEFAULT_IMAGE_TOKEN = "<image>"          # src/xtuner/xtuner/utils/constants.py:5
 IMAGE_TOKEN_INDEX = -200                 # constants.py:4
@@ -72,6 +73,15 @@ class AuroraEncoder:
         return self._e.vit_encode(pixel_values, r)
 
 
+class GenerateOutput:
+    """What `_LLM.generate(return_dict_in_generate=True)` returns: `sequences` LongTensor [1, n] (what the plain call returns) and,
+    with output_logprobs=True, `token_logprobs` float32 [1, n], `top_ids` long [1, n, k], `top_logprobs` float32 [1, n, k]
+    (k = top_logprobs; `aurora_amd.scoring.token_logprobs` is the definition) - else None."""
+
+    def __init__(self, sequences, token_logprobs=None, top_ids=None, top_logprobs=None):
+        self.sequences, self.token_logprobs, self.top_ids, self.top_logprobs = sequences, token_logprobs, top_ids, top_logprobs
+
+
 class _LLM:
     def __init__(self, engine: AuroraCapEngine, eos_token_id: Optional[int]):
         self._e = engine
@@ -82,14 +92,21 @@ class _LLM:
     def generate(self, inputs_embeds: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.0, top_p: float = 1.0,
                  num_beams: int = 1, max_new_tokens: int = 2048, input_ids=None, position_ids=None, attention_mask=None,
                  past_key_values=None, labels=None, eos_token_id="default", top_k="default", seed: int = 0, stream: int = 0,
-                 **unused) -> torch.Tensor:
+                 output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False, **unused):
         """do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
         sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
         passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
         ids are a function of (seed, stream) and the prompt alone.
         top_k follows the transformers range the reference pins (<= 4.42), whose GenerationConfig defaults it to 50 - later
         releases report None -; a `top_k` in the checkpoint's generation_config.json (`self.generation_top_k`) wins over that default,
-        an explicit argument over both; top_k=0 turns the filter off."""
+        an explicit argument over both; top_k=0 turns the filter off.
+        return_dict_in_generate=True: a `GenerateOutput` instead of the ids tensor; with output_logprobs=True it carries the
+        log-probability of every generated token and its `top_logprobs` (0 .. 8) most likely alternatives, under the model's
+        unmodified distribution whatever do_sample says.  output_logprobs=True needs return_dict_in_generate=True (ValueError);
+        `output_scores` stays ignored."""
+        if output_logprobs and not return_dict_in_generate:
+            raise ValueError("output_logprobs=True needs return_dict_in_generate=True (the plain call returns the ids tensor alone)")
+        lpn = check_logprobs(top_logprobs) if output_logprobs else None
         if inputs_embeds is None:
             raise ValueError("generate() on this path takes inputs_embeds (the output of model(data, mode='inference'))")
         if num_beams != 1:
@@ -106,8 +123,14 @@ class _LLM:
         pad = torch.zeros((L + 31) // 32 * 32, d, dtype=torch.float16, device=self._e.dev)
         pad[:L] = inputs_embeds[0].to(device=self._e.dev, dtype=torch.float16)
         n = min(max_new_tokens, self._e.max_new_tokens)
-        ids = self._e.generate([pad], [L], n, eos_id=eos, **(dict(sampling=sampling, streams=[stream]) if sampling else {}))[0]
-        return torch.tensor([ids], dtype=torch.long)
+        kw = dict(sampling=sampling, streams=[stream]) if sampling else {}
+        if lpn is None:
+            ids = self._e.generate([pad], [L], n, eos_id=eos, **kw)[0]
+            seq = torch.tensor([ids], dtype=torch.long)
+            return GenerateOutput(seq) if return_dict_in_generate else seq
+        r = self._e.generate([pad], [L], n, eos_id=eos, logprobs=lpn, **kw)[0]
+        return GenerateOutput(torch.tensor([r["ids"]], dtype=torch.long), torch.from_numpy(r["token_logprobs"]).unsqueeze(0),
+                              torch.from_numpy(r["top_ids"].astype("int64")).unsqueeze(0), torch.from_numpy(r["top_logprobs"]).unsqueeze(0))
 
 
 class AuroraModel:
@@ -128,13 +151,16 @@ class AuroraModel:
         model.llm.generation_top_k = generation_top_k(path)
         return model
 
-    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None):
+    def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None,
+                      logprobs: Optional[int] = None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
         sampling=dict(temperature, top_k, top_p, seed): sampled captions, clip i drawing with stream streams[i] (default: i).
         share: one hashable key per clip (or None); clips of equal key are the same visual input and share its ViT pass and the KV
-        of their common prefix inside a chunk of max_batch clips (AuroraCapEngine.caption_batch)."""
+        of their common prefix inside a chunk of max_batch clips (AuroraCapEngine.caption_batch).
+        logprobs=n (0 .. 8): a dict per clip instead - ids, token_logprobs, top_ids, top_logprobs (AuroraCapEngine.generate)."""
+        check_logprobs(logprobs)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
@@ -145,6 +171,8 @@ class AuroraModel:
             kw = dict(sampling=sampling, streams=st) if sampling is not None else {}
             if share is not None:
                 kw["share"] = list(share)[c0:c0 + len(group)]
+            if logprobs is not None:
+                kw["logprobs"] = logprobs
             out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 

@@ -44,6 +44,59 @@ def score_rows(logits: np.ndarray, targets: Sequence[int]) -> Tuple[np.ndarray, 
     return lp, am
 
 
+# ---------------------------------------------------------------------------------------- log-probabilities of GENERATED tokens
+# The token a generation step picked from an fp32 logits row l - by the greedy or by the sampled pick - has the log-probability
+# `score_row` gives it under that row: the model's UNMODIFIED distribution (temperature, top-k and top-p do not enter; the rule of the
+# reference tree's serving engine, sglang/srt/layers/logits_processor.py:187-218), so greedy captions, sampled captions and
+# `loglikelihood` speak of one quantity.  Its top-n alternatives, 0 <= n <= MAX_TOP_LOGPROBS, are the first n entries of the row in the
+# order (value descending, index ascending), each with its own lp: rank 0 is `score_row`'s first argmax with lp = -log S, ties go to
+# the lower index (the all-equal row gives ids 0 .. n-1), ranks at or beyond the vocabulary are (-1, 0.0).  A token outside [0, vocab)
+# marks an unused entry, as in `score_rows`: lp = 0, every rank (-1, 0.0).  A row without a maximum (all NaN) follows `score_row`:
+# rank 0 is token 0, and nothing is behind it.
+MAX_TOP_LOGPROBS = 8
+
+
+def check_logprobs(logprobs):
+    """The `logprobs=` argument of the generation calls: None (off) or an int in [0, MAX_TOP_LOGPROBS] -> None or that int."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)):
+        raise ValueError(f"logprobs must be None or an int in [0, {MAX_TOP_LOGPROBS}], got {logprobs!r}")
+    if not 0 <= int(logprobs) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs={int(logprobs)} outside [0, {MAX_TOP_LOGPROBS}]")
+    return int(logprobs)
+
+
+def token_logprobs(logits: np.ndarray, token: int, top_n: int = 0) -> Tuple[float, np.ndarray, np.ndarray]:
+    """(lp of `token`, top ids int32 [top_n], their lp float64 [top_n]) of one logits row, in float64."""
+    top_n = check_logprobs(top_n)
+    l = np.asarray(logits, dtype=np.float64).reshape(-1)
+    ids, lps = np.full(top_n, -1, np.int32), np.zeros(top_n, np.float64)
+    t = int(token)
+    if not 0 <= t < l.shape[0]:
+        return 0.0, ids, lps
+    lp, a = score_row(l, t)
+    log_s = np.log(np.sum(np.exp(l - l[a])))
+    order = np.argsort(-l, kind="stable")                  # value descending, index ascending among equals; NaN last
+    order = order[~np.isnan(l[order])]
+    if order.shape[0] == 0:
+        order = np.array([a])                              # no maximum: score_row's token alone
+    k = min(top_n, order.shape[0])
+    ids[:k] = order[:k]
+    lps[:k] = (l[order[:k]] - l[a]) - log_s
+    return lp, ids, lps
+
+
+def token_logprob_rows(logits: np.ndarray, tokens: Sequence[int], top_n: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`token_logprobs` over the rows of a [rows, vocab] array -> (float64 [rows], int32 [rows, top_n], float64 [rows, top_n])."""
+    lg = np.asarray(logits)
+    n = len(tokens)
+    lp, ids, lps = np.zeros(n, np.float64), np.full((n, top_n), -1, np.int32), np.zeros((n, top_n), np.float64)
+    for j, t in enumerate(tokens):
+        lp[j], ids[j], lps[j] = token_logprobs(lg[j], int(t), top_n)
+    return lp, ids, lps
+
+
 def score_continuation(logits: np.ndarray, continuation: Sequence[int]) -> Tuple[float, bool, List[float]]:
     """logits [n, vocab]: the rows that predict continuation[0 .. n) -> (sum_logprob, is_greedy, per-token log-probabilities)."""
     cont = [int(t) for t in continuation]

@@ -249,7 +249,8 @@ int aur_slot_collect(aur_ctx* ctx, int32_t slot0, int32_t nslots, int32_t* ids_d
  * current bank (whose page table the prefill writes through) are frozen at capture time: a serving loop keeps one graph per (bank,
  * frames, input size, r, prompt structure, target sequences) bucket and copies each clip's pixels / ids into the bucket's staging
  * buffers before the replay (aurora_amd/engine.py FrontEndGraph).  Calls that synchronise or re-capture (aur_get_outputs,
- * aur_unfinished, aur_slot_state, aur_microbench, aur_decode_stamps_read, aur_begin_batch, aur_set_option, aur_finalize,
+ * aur_unfinished, aur_slot_state, aur_microbench, aur_decode_stamps_read, aur_begin_batch, aur_set_option, aur_logprob_enable,
+ * aur_get_logprobs, aur_finalize,
  * aur_profile_enable), aur_select_bank (it would split the capture between two banks) and aur_llm_decode (it replays its own graph)
  * return AUR_ERR_STATE inside a capture without touching the runtime: the capture stays valid, and aur_graph_end - which must be called
  * in any case - closes it.  A synchronising HIP call of the CALLER's own inside the capture invalidates it: aur_graph_end then returns
@@ -376,6 +377,38 @@ int aur_llm_score_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, in
                       int64_t scratch_bytes, float* logprob_out, int32_t* argmax_out, float* logits_out, void* stream);
 int aur_score_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* targets_dev, float* logprob_out,
                    int32_t* argmax_out, void* stream);
+
+/* ---- log-probabilities of GENERATED tokens, with top-n alternatives (the reference tree's serving engine offers
+ * it per request as return_logprob / top_logprobs_num, from log_softmax of the raw last-position logits:
+ * sglang/srt/layers/logits_processor.py:187-218).  aurora_amd/scoring.py token_logprobs is the definition in numpy.
+ * For the fp32 logits row l a token t was picked from - by the greedy or the sampled pick; temperature, top-k and top-p do not enter -:
+ * lp(t) = (l[t] - m) - log(sum exp(l[i] - m)), bitwise what aur_score_rows says about that row; and the first top_n (0 .. 8) entries
+ * of the row in the order (value descending, index ascending), each with its lp: rank 0 is aur_score_rows' argmax, ties go to the
+ * lower index, ranks at or beyond vocab are (-1, 0.0).
+ * The state of one bank lives in a CALLER-OWNED device buffer of aur_logprob_bytes bytes (16-byte aligned; the layout is the library's
+ * business): nothing is allocated here, aur_workspace_bytes does not grow, and a process that never asks launches exactly what it did.
+ * aur_logprob_enable acts on the CURRENT bank: resets the buffer on the stream (no slot holds a record) and, from then on, every
+ * prefill's first token, every commit and every decode step - captured or eager - is followed by one more launch that records the
+ * newest token of each slot that appended one.  buf_dev == NULL turns it off again.  Call it before aur_begin_batch.  The choice is
+ * frozen in the bank's captured decode graphs, which the call drops (as option "sampling" does), and in a CALLER's capture that holds a
+ * prefill / commit / aur_slot_reset, which the caller re-captures; AUR_ERR_STATE inside aur_graph_begin / aur_graph_end.
+ * aur_begin_batch, aur_slot_reset and the commits clear the records of the slots whose lengths they clear.
+ * aur_get_logprobs (synchronises, like aur_get_outputs): lp_host fp32 [batch * max_new_tokens], top_ids_host int32 / top_lp_host fp32
+ * [batch * max_new_tokens * top_n] (NULL to skip), lens_host [batch] = tokens recorded per slot (= the slot's generated length); entries
+ * at or beyond a slot's length are 0 / (-1, 0.0).  max_new_tokens: the batch's, as for aur_get_outputs.
+ * aur_slot_collect_logprobs: the same for slots [slot0, slot0 + nslots) device-to-device, enqueue-only and recordable like
+ * aur_slot_collect.
+ * aur_token_logprob_rows: the kernel alone on caller rows.  logits fp32 [rows, vocab] device; tokens_dev int32 [rows]; lp_out fp32
+ * [rows]; top_ids_out int32 / top_lp_out fp32 [rows, top_n] (NULL allowed for top_n == 0).  A pure function of the row's values: the
+ * same bits at any row index, row count or alignment.  A token outside [0, vocab) marks an unused entry: lp 0, every rank (-1, 0.0),
+ * the row is not read. */
+int64_t aur_logprob_bytes(const aur_ctx* ctx, int32_t top_n);      /* -1: top_n outside [0, 8] */
+int aur_logprob_enable(aur_ctx* ctx, int32_t top_n, void* buf_dev, int64_t nbytes, void* stream);
+int aur_get_logprobs(aur_ctx* ctx, float* lp_host, int32_t* top_ids_host, float* top_lp_host, int32_t* lens_host, void* stream);
+int aur_slot_collect_logprobs(aur_ctx* ctx, int32_t slot0, int32_t nslots, float* lp_dev, int32_t* top_ids_dev, float* top_lp_dev,
+                              int32_t* lens_dev, void* stream);
+int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* tokens_dev, int32_t top_n,
+                           float* lp_out, int32_t* top_ids_out, float* top_lp_out, void* stream);
 
 /* Tuning knobs.  Invalidate the captured decode graphs (of every bank): "decode_fused_reduce" 0 (default: the split-K residual projections are followed
  * by a reduce launch) / 1 (the last-arriving split reduces inside the kernel; bitwise the same), "dec_attn_local" 1 (default: on engines

@@ -48,13 +48,33 @@ def build_parser() -> argparse.ArgumentParser:
                         help='instead of generating: print the log-likelihood of TEXT as the answer to --prompt (the sum of its tokens\' '
                              'log-probabilities), with is_greedy (every token of TEXT is the greedy pick) and the token count; '
                              'with --synthetic there is no tokenizer: the text is ignored and a seeded answer of 8 tokens is scored')
+    parser.add_argument('--logprobs', type=int, default=None, metavar='N',
+                        help='after the caption: one line per generated token - id, decoded piece, log-probability under the model\'s '
+                             'unmodified distribution, and its N (0 .. 8) most likely alternatives -, then their sum and exp(-mean)')
     return parser
+
+
+def print_logprobs(out, tokenizer):
+    """One line per generated token: `token <i> id <id> <piece> logprob <lp> top <id>:<lp> ...`; then `sum_logprob <s> perplexity <p>`."""
+    ids, lps = out.sequences[0].tolist(), out.token_logprobs[0].tolist()
+    piece = (lambda t: repr(str(t))) if tokenizer is None else (lambda t: repr(tokenizer.convert_ids_to_tokens(int(t))))
+    for i, (t, lp) in enumerate(zip(ids, lps)):
+        alts = " ".join(f"{int(a)}:{float(v)!r}" for a, v in zip(out.top_ids[0, i].tolist(), out.top_logprobs[0, i].tolist()))
+        print(f"token {i} id {t} {piece(t)} logprob {float(lp)!r} top {alts}".rstrip())
+    total = 0.0
+    for lp in lps:
+        total += float(lp)
+    print(f"sum_logprob {total!r} perplexity {float(np.exp(-total / max(len(lps), 1)))!r}")
 
 
 def main():
     args = build_parser().parse_args()
     if args.do_sample and not args.temperature > 0:
         sys.exit("error: --do_sample needs --temperature > 0 (the reference CLI's default temperature, 0.0, is kept: it means greedy)")
+    if args.logprobs is not None and not 0 <= args.logprobs <= 8:
+        sys.exit("error: --logprobs takes a number of alternatives in [0, 8]")
+    if args.logprobs is not None and (args.extra_prompt or args.score is not None):
+        sys.exit("error: --logprobs goes with one generated caption (not with --extra_prompt or --score)")
     if args.num_beams != 1:
         sys.exit("error: beam search is not implemented on the MI355X path: generation is greedy or, with --do_sample, sampled (--num_beams 1)")
 
@@ -145,11 +165,18 @@ def main():
     output = model(data, mode="inference")
     sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
     cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
-                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample)
+                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample,
+                              **(dict(return_dict_in_generate=True, output_logprobs=True, top_logprobs=args.logprobs)
+                                 if args.logprobs is not None else {}))
+    lp_out = None
+    if args.logprobs is not None:
+        lp_out, cont = cont, cont.sequences
     if tokenizer is None:
         print(cont[0].tolist())
     else:
         print(tokenizer.batch_decode(cont, skip_special_tokens=True)[0])
+    if lp_out is not None:
+        print_logprobs(lp_out, tokenizer)
 
 
 if __name__ == "__main__":
