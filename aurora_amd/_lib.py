@@ -41,6 +41,11 @@ class AurSampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("stream", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class AurLogitRules(C.Structure):
+    """aur_logit_rules: one slot's logit rules (aurora_amd.logit_rules.RECORD is the numpy form of the same layout)"""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int32), ("min_new_tokens", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AuroraHipError(RuntimeError):
     pass
 
@@ -103,6 +108,8 @@ SIGNATURES = {
     "aur_vit_layer": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aur_slot_sampling": (C.c_int, [_P, _I, _I, _P, _P]),
     "aur_sample_rows": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "aur_slot_logit_rules": (C.c_int, [_P, _I, _I, _P, _P]),
+    "aur_logit_rules_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
     "aur_attn_rows": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
     "aur_attn_decode_scratch_bytes": (_L, [_P, _I]),
     "aur_attn_decode_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _L, _P, _P]),

@@ -85,6 +85,7 @@ struct aur_ctx {
     int attn_local = 1;                                                         // 1: workgroup-local join of the decode attention's splits where it applies (mk_dec_attn); 0 = always decode_attn_combine_kernel (A/B and test)
     int tome_fused_ln = 1;                                                      // 1: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge launch (bitwise norm_kernel's result; 0 = its own launch, A/B and test only)
     int sampling = 0, sample_stage = 1;                                         // the token pick: 0 argmax_advance_kernel, 1 sample_advance_kernel (row staged in LDS / re-read from L2)
+    int logit_rules = 0;                                                        // 1: logit_rules_apply_kernel ahead of every pick, logit_rules_restore_kernel behind it (the slots' aur_logit_rules records)
     int fused_reduce = 0;                                                       // 1: the split-K reduce runs inside the projection kernel
     // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graphs) so
     // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  Every generation call
@@ -95,6 +96,9 @@ struct aur_ctx {
         float* d_logits;
         int32_t *s_pos, *s_ids, *s_len, *s_fin;
         aur_sampling* s_samp;                                // per-slot sampling parameters (aur_slot_sampling); temperature 0 = greedy
+        aur_logit_rules* s_rules;                            // per-slot logit rules (aur_slot_logit_rules); all zero = neutral
+        int32_t* lr_cnt;                                     // entries of each slot's side list written by the last apply
+        void* lr_save = nullptr;                             // side lists [max_batch][max_new_tokens + 1] of (index, original logit): allocated by option "logit_rules" 1
         int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
         // log-probabilities of generated tokens (aur_logprob_enable): the caller's buffer, nullptr = off.  lp_len [max_batch]: tokens of
         // slot b recorded so far; lp [b][max_new], lp_top_id / lp_top_lp [b][max_new][lp_top_n]: rows max_new apart, like s_ids
@@ -296,6 +300,8 @@ static int64_t carve(aur_ctx* c, char* base) {
         K.s_len = k.take<int32_t>(B);
         K.s_fin = k.take<int32_t>(B);
         K.s_samp = k.take<aur_sampling>(B);
+        K.s_rules = k.take<aur_logit_rules>(B);
+        K.lr_cnt = k.take<int32_t>(B);
     }
     c->d_q = k.take<half_t>(B * d);
     c->d_attn = k.take<half_t>(Bp * d);                    // attention output  (x-fragment form)
@@ -357,7 +363,10 @@ static void drop_graphs(aur_ctx::Bank& K) {
 
 extern "C" void aur_destroy(aur_ctx* ctx) {
     if (!ctx) return;
-    for (auto& K : ctx->banks) drop_graphs(K);
+    for (auto& K : ctx->banks) {
+        drop_graphs(K);
+        if (K.lr_save) (void)hipFree(K.lr_save);
+    }
     for (auto& ug : ctx->ugraphs)
         if (ug.exec) (void)hipGraphExecDestroy(ug.exec);
     for (auto& kv : ctx->timers) {
@@ -966,6 +975,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.s_fin, 0, (size_t)g.max_batch * 4, s));
     CK(hipMemsetAsync(K.s_pos, 0, (size_t)g.max_batch * 4, s));
     CK(hipMemsetAsync(K.s_samp, 0, (size_t)g.max_batch * sizeof(aur_sampling), s));      // every slot greedy until aur_slot_sampling says otherwise
+    CK(hipMemsetAsync(K.s_rules, 0, (size_t)g.max_batch * sizeof(aur_logit_rules), s));  // every slot neutral until aur_slot_logit_rules says otherwise
     CK(hipMemsetAsync(K.s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
     const size_t bp = (size_t)rup(g.max_batch, 16);       // unused fragment lanes must hold finite values
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
@@ -985,12 +995,16 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     h.mode = SK_LOGITS; h.out32 = K.d_logits; h.b_lo = b0; h.b_hi = b0 + nb; h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
     h.variant = ctx->skinny_variant;
     CK(launch_skinny(h, s));
+    // logit rules: the affected entries of the rows are rewritten for the pick alone; behind it the rows are the model's again
+    if (ctx->logit_rules)
+        CK(launch_logit_rules_apply(K.d_logits, b0, nb, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
     if (ctx->sampling)
         CK(launch_sample_advance(K.d_logits, b0, nb, g.llm_vocab, K.s_samp, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
                                  K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap, ctx->sample_stage));
     else
         CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
                                  K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
+    if (ctx->logit_rules) CK(launch_logit_rules_restore(K.d_logits, b0, nb, g.llm_vocab, K.max_new, K.lr_save, K.lr_cnt, s));
     // the log-probability of what was just picked, under the row it was picked from: a launch of its own behind the pick, which stays as it is
     if (K.lp_len)
         CK(launch_token_logprob(K.d_logits, b0, nb, g.llm_vocab, K.s_ids, K.s_len, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id,
@@ -1833,6 +1847,7 @@ extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     CK(hipMemsetAsync(K.s_fin + slot, 0, 4, s));
     CK(hipMemsetAsync(K.s_pos + slot, 0, 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
+    CK(hipMemsetAsync(K.s_rules + slot, 0, sizeof(aur_logit_rules), s));
     return logprob_clear(ctx, K, slot, 1, s);
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
@@ -1950,6 +1965,30 @@ extern "C" int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, 
     CK(launch_sample_rows(logits, rows, vocab, params_dev, n_dev, tokens_out, kept_out, (hipStream_t)stream, ctx->sample_stage));
     return AUR_OK;
 }
+extern "C" int aur_slot_logit_rules(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_logit_rules* rules_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_logit_rules")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (nslots < 1 || slot0 + nslots > K.batch || !rules_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_logit_rules: slots [%d, %d) outside the batch of %d, or null rules", slot0, slot0 + nslots, K.batch);
+    CK(hipMemcpyAsync(K.s_rules + slot0, rules_dev, (size_t)nslots * sizeof(aur_logit_rules), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AUR_OK;
+}
+extern "C" int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const int32_t* ids_dev, int32_t ids_stride,
+                                    const int32_t* lens_dev, const aur_logit_rules* rules_dev, int32_t eos_id, int32_t restore, void* stream) {
+    if (!ctx || !logits || !ids_dev || !lens_dev || !rules_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_logit_rules_rows: null argument");
+    NO_CAPTURE("aur_logit_rules_rows");
+    if (rows < 1 || rows > 65535 || vocab < 1 || ids_stride < 1)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_logit_rules_rows: rows %d outside [1, 65535], vocab %d < 1 or ids_stride %d < 1", rows, vocab, ids_stride);
+    hipStream_t s = (hipStream_t)stream;
+    char* side = nullptr;
+    const int64_t list = logit_rules_save_bytes(rows, ids_stride);                     // the side lists, then the counts
+    CK(hipMalloc((void**)&side, (size_t)list + (size_t)rows * 4));
+    hipError_t e = launch_logit_rules_apply(logits, 0, rows, vocab, rules_dev, ids_dev, ids_stride, lens_dev, eos_id, side, (int32_t*)(side + list), s);
+    if (e == hipSuccess && restore) e = launch_logit_rules_restore(logits, 0, rows, vocab, ids_stride, side, (const int32_t*)(side + list), s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(side);
+    CK(e);
+    return AUR_OK;
+}
 extern "C" int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream) {
     const aur_ctx::Bank& K = ctx->bank();
     if (K.batch < 1 || !dst_dev) return aur_fail(ctx, AUR_ERR_STATE, "aur_copy_logits: no active batch");
@@ -1999,6 +2038,15 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
         // which kernel picks the token (and how it reads its row) is frozen inside the captured decode graphs: they are re-captured
         if (value < 0 || value > 1) return aur_fail(ctx, AUR_ERR_ARG, "%s must be 0 or 1", name);
         (!strcmp(name, "sampling") ? ctx->sampling : ctx->sample_stage) = (int)value;
+    } else if (!strcmp(name, "logit_rules")) {
+        // whether the two launches bracket the pick is frozen inside the captured decode graphs, like "sampling": they are re-captured.
+        // The side lists are allocated here, once, outside any capture; they live as long as the ctx
+        if (value < 0 || value > 1) return aur_fail(ctx, AUR_ERR_ARG, "%s must be 0 or 1", name);
+        if (value)
+            for (int bk = 0; bk < 2; ++bk)
+                if (!ctx->banks[bk].lr_save)
+                    CK(hipMalloc(&ctx->banks[bk].lr_save, (size_t)logit_rules_save_bytes(ctx->cfg.max_batch, ctx->cfg.max_new_tokens)));
+        ctx->logit_rules = (int)value;
     } else if (!strcmp(name, "decode_half_grid")) {
         // the following aur_llm_decode calls go to a stream that owns half of the CUs: QKV / gate-up launch half as many workgroups
         // with twice the tiles (decode.hip launch_skx_nb); bitwise the same tokens.  Keeps both captured graphs.
@@ -2046,6 +2094,10 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
             else
                 CK(launch_argmax_advance(K.d_logits, 0, K.batch, g.llm_vocab, ctx->l_embed, d, K.eos, K.max_new, K.s_ids, K.s_len, K.s_fin, K.s_pos,
                                          K.d_x, K.s_ssq_mlp, 1, -1, s));
+        } else if (!strcmp(kernel, "dec_rules")) {             // the logit rules' two launches, on the logits and the history of the last step
+            if (!ctx->logit_rules) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_rules needs option \"logit_rules\" 1");
+            CK(launch_logit_rules_apply(K.d_logits, 0, K.batch, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
+            CK(launch_logit_rules_restore(K.d_logits, 0, K.batch, g.llm_vocab, K.max_new, K.lr_save, K.lr_cnt, s));
         } else {
             int bit = !strcmp(kernel, "pre_norm") ? 1 : !strcmp(kernel, "pre_qkv") ? 2 : !strcmp(kernel, "pre_attn") ? 4 : !strcmp(kernel, "pre_o") ? 8
                       : !strcmp(kernel, "pre_gateup") ? 32 : !strcmp(kernel, "pre_down") ? 64 : 0;

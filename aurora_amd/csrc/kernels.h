@@ -216,6 +216,16 @@ hipError_t launch_sample_advance(const float* logits, int b0, int nb, int vocab,
 hipError_t launch_sample_rows(const float* logits, int rows, int vocab, const aur_sampling* params, const int32_t* n_dev,
                               int32_t* tokens_out, int32_t* kept_out, hipStream_t s, int stage);
 
+// ---- logit_rules.hip: repetition penalty / no-repeat n-gram / min-new-tokens on the logits rows of slots [b0, b0 + nb) ahead of the
+// pick, and the originals back behind it.  ids [.., ids_stride] / lens: the slots' generated tokens; save: logit_rules_save_bytes(slots,
+// ids_stride) bytes (ids_stride + 1 entries per slot), save_cnt int32 [slots]
+struct aur_logit_rules;
+int64_t logit_rules_save_bytes(int rows, int ids_stride);
+hipError_t launch_logit_rules_apply(float* logits, int b0, int nb, int vocab, const aur_logit_rules* rules, const int32_t* ids, int ids_stride,
+                                    const int32_t* lens, int eos_id, void* save, int32_t* save_cnt, hipStream_t s);
+hipError_t launch_logit_rules_restore(float* logits, int b0, int nb, int vocab, int ids_stride, const void* save, const int32_t* save_cnt,
+                                      hipStream_t s);
+
 // ---- score.hip: log-probability of a target token under a logits row (+ the row's first argmax), and the row-list gather that feeds
 // any rows of a prefill pass to the pick path's lm_head (aur_llm_score_var)
 hipError_t launch_score_rows(const float* logits, int rows, int vocab, const int32_t* targets, float* logprob_out, int32_t* argmax_out,

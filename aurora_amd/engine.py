@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import logit_rules as LR
 from . import sampling as S
 from .scoring import check_logprobs
 from ._lib import AurConfig, check
@@ -335,6 +336,8 @@ class AuroraCapEngine:
         self._bank = 0
         self._sampling_mode = False                      # ctx option "sampling": flipped by the first sampling request, sticky
         self._samp_stage = None                          # device staging of aur_sampling records, one row per (bank, slot)
+        self._rules_mode = False                         # ctx option "logit_rules": flipped by the first request with non-neutral rules, sticky
+        self._rules_stage = None                         # device staging of aur_logit_rules records, one row per (bank, slot)
         self._lp_bufs: Dict[int, torch.Tensor] = {}      # bank -> the caller-owned state of aur_logprob_enable (kept once allocated)
         self._lp_top: Dict[int, int] = {}                # bank -> top_n it records with; absent = off
         self.c = c
@@ -990,8 +993,73 @@ class AuroraCapEngine:
         """The first sampling request switches the ctx's token pick to sample_advance_kernel (decode graphs are re-captured once);
         slots whose temperature is 0 keep the greedy rule bit for bit.  A process that never samples never gets here."""
         if not self._sampling_mode:
+            self._drop_front_graphs()
             self.set_option("sampling", 1)
             self._sampling_mode = True
+
+    def _drop_front_graphs(self):
+        """Before an option that changes which kernels a prefill / commit launches is flipped: no front-end graph captured under
+        the old setting is replayed under the new one (today's graphs hold the stage only - the pick is the eager commit's - so this
+        is the guard for one that captures a commit, as `graph_capture` allows)."""
+        for fg in self._front_graphs.values():
+            if getattr(fg, "_last", None) is not None:
+                fg._last.synchronize()
+            fg.close()
+        self._front_graphs = {}
+
+    # ------------------------------------------------------------------ logit rules
+    def _rules_on(self):
+        """The first request with non-neutral logit rules brackets the ctx's token pick with logit_rules_apply_kernel /
+        logit_rules_restore_kernel (decode graphs are re-captured once, the side lists are allocated); slots whose record is
+        neutral are not touched.  Sticky, like `_sampling_on`.  A process that never asks never gets here."""
+        if not self._rules_mode:
+            self._drop_front_graphs()
+            self.set_option("logit_rules", 1)
+            self._rules_mode = True
+
+    def slot_logit_rules(self, slot0: int, recs: np.ndarray):
+        """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_logit_rules records (`logit_rules.records`): staged
+        in device memory and copied into the bank when the stream gets there - before the prefill / commit that picks the first
+        token.  The history the rules see is the slot's generated tokens, not its prompt."""
+        recs = np.ascontiguousarray(recs, dtype=LR.RECORD)
+        n = len(recs)
+        if n < 1 or slot0 < 0 or slot0 + n > self.max_batch:
+            raise ValueError(f"slots [{slot0}, {slot0 + n}) outside an engine of {self.max_batch} slots")
+        if self._rules_stage is None:
+            self._rules_stage = torch.zeros(2 * self.max_batch, LR.RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        row0 = self._bank * self.max_batch + slot0
+        dst = self._rules_stage[row0: row0 + n]
+        dst.copy_(torch.from_numpy(recs.view(np.uint8).reshape(n, LR.RECORD.itemsize).copy()))     # torch's current stream: _stream() orders ours behind it
+        check(self.ctx, self.L.aur_slot_logit_rules(self.ctx, slot0, n, dst.data_ptr(), self._stream()), "aur_slot_logit_rules")
+
+    def logit_rules_rows(self, logits: torch.Tensor, histories: Sequence[Sequence[int]], recs: np.ndarray, eos_id: Optional[int],
+                         restore: bool = False, ids_stride: Optional[int] = None) -> torch.Tensor:
+        """The rule kernels alone (aur_logit_rules_rows) on a copy of `logits` (fp32 [rows, vocab] on the device): one generated
+        history and one aur_logit_rules record per row -> the processed rows (restore=False) or the rows after apply + restore
+        (restore=True), on the device.  ids_stride: the row stride of the history buffer (default: the longest history, at least 1)."""
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.is_contiguous() and logits.dim() == 2
+        rows, vocab = logits.shape
+        recs = np.ascontiguousarray(recs, dtype=LR.RECORD)
+        assert len(recs) == rows and len(histories) == rows
+        stride = max([1] + [len(h) for h in histories]) if ids_stride is None else int(ids_stride)
+        assert stride >= 1 and all(len(h) <= stride for h in histories)
+        ids = np.zeros((rows, stride), np.int32)
+        for i, h in enumerate(histories):
+            ids[i, :len(h)] = np.asarray(h, np.int32)
+        ids_d = torch.from_numpy(ids).to(self.dev)
+        lens_d = torch.tensor([len(h) for h in histories], dtype=torch.int32, device=self.dev)
+        rec_d = torch.from_numpy(recs.view(np.uint8).reshape(rows, LR.RECORD.itemsize).copy()).to(self.dev)
+        out = logits.clone()
+        check(self.ctx, self.L.aur_logit_rules_rows(self.ctx, out.data_ptr(), rows, vocab, ids_d.data_ptr(), stride, lens_d.data_ptr(),
+                                                    rec_d.data_ptr(), -1 if eos_id is None else int(eos_id), 1 if restore else 0,
+                                                    self._stream()), "aur_logit_rules_rows")
+        torch.cuda.synchronize()
+        return out
+
+    def _begin_rules(self, rules: Optional[dict], B: int):
+        """After begin_batch (which makes every slot neutral): the records of slots [0, B) for a call with logit rules."""
+        if rules is not None:
+            self.slot_logit_rules(0, LR.records(rules, B))
 
     def slot_sampling(self, slot0: int, recs: np.ndarray):
         """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_sampling records (`sampling.records`): staged in
@@ -1033,22 +1101,31 @@ class AuroraCapEngine:
         return tok.cpu().numpy(), kept.cpu().numpy()
 
     def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
-                 sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None):
+                 sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None,
+                 logit_rules: Optional[dict] = None):
         """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
         sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
         the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours.
         logprobs=n (0 .. 8): each result is a dict - ids, token_logprobs float32 [len], top_ids int32 [len, n], top_logprobs float32
         [len, n] - as `scoring.token_logprobs` defines them: under the model's unmodified distribution, whatever `sampling` says;
-        the ids are the same.  None: the list of ids, and no extra work."""
+        the ids are the same.  None: the list of ids, and no extra work.
+        logit_rules=dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0), one dict for the call: transformers'
+        three processors on the raw row ahead of the pick, greedy or sampled, as `aurora_amd.logit_rules` defines them - over the
+        tokens GENERATED so far, never the prompt (what `generate(inputs_embeds=...)` gives the reference).  Log-probabilities stay
+        those of the unmodified row.  None or all-neutral values: exactly the path of a call without the argument."""
         lpn = check_logprobs(logprobs)
         B = len(embeds_list)
         samp = S.check_sampling(sampling)
+        rules = LR.check_logit_rules(logit_rules)
         if samp is not None:
             self._sampling_on()
+        if rules is not None:
+            self._rules_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
+        self._begin_rules(rules, B)
         for b in range(B):
             self.prefill(b, embeds_list[b], seq_lens[b])
         done = 1
@@ -1061,17 +1138,22 @@ class AuroraCapEngine:
         return self.outputs(lpn)
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
-                    eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None):
-        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs: as in `generate`."""
+                    eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None,
+                    logit_rules: Optional[dict] = None):
+        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules: as in
+        `generate`."""
         check_logprobs(logprobs)
+        LR.check_logit_rules(logit_rules)
         r = self.tome_r(token_kept_ratio, pixels.shape[-2], pixels.shape[-1])
         vis = self.vit_encode(pixels, r)
         emb, L = self.project_splice(vis, input_ids)
-        return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream], logprobs=logprobs)[0]
+        return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream], logprobs=logprobs,
+                             logit_rules=logit_rules)[0]
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
-                      streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None):
+                      streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None,
+                      logit_rules: Optional[dict] = None):
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
@@ -1083,10 +1165,12 @@ class AuroraCapEngine:
         clip's slot (`kv_copy_prefix`) and prefills only its remaining rows, neighbouring siblings in one pass (`extend_batch`).  A
         sibling whose prompt shares less than a page with the first clip's, or diverges from it before the visual rows end, takes the
         unshared path.  The same ids either way; share=None is exactly the path above.
-        logprobs=n: a dict per clip instead of its ids, as in `generate`."""
+        logprobs=n: a dict per clip instead of its ids, as in `generate`.
+        logit_rules: one dict for every clip of the call, as in `generate` (each clip's own generated tokens are its history)."""
         lpn = check_logprobs(logprobs)
         B = len(clips)
         samp = S.check_sampling(sampling)
+        rules = LR.check_logit_rules(logit_rules)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{B} clips for an engine built with max_batch={self.max_batch}")
         if share is not None and len(share) != B:
@@ -1112,10 +1196,13 @@ class AuroraCapEngine:
         vis_of = {}
         if samp is not None:
             self._sampling_on()
+        if rules is not None:
+            self._rules_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
+        self._begin_rules(rules, B)
         runs, b0 = [], 0                                          # maximal runs of neighbouring clips that are nobody's sibling
         for i in range(B + 1):
             if i == B or i in child:
@@ -1164,10 +1251,12 @@ class AuroraCapEngine:
 
     def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
                         eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None,
-                        logprobs: Optional[int] = None):
+                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None):
         """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
-        (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs: as in `generate`."""
+        (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs / logit_rules: as
+        in `generate`."""
         check_logprobs(logprobs)
+        LR.check_logit_rules(logit_rules)
         prompts = [list(ids) for ids in list_of_input_ids]
         st = list(range(len(prompts))) if streams is None else [int(x) for x in streams]
         out: List[List[int]] = []
@@ -1175,7 +1264,8 @@ class AuroraCapEngine:
             chunk = prompts[c0:c0 + self.max_batch]
             out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
                                       streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk),
-                                      **({} if logprobs is None else dict(logprobs=logprobs)))
+                                      **({} if logprobs is None else dict(logprobs=logprobs)),
+                                      **({} if logit_rules is None else dict(logit_rules=logit_rules)))
         return out
 
     # ------------------------------------------------------------------ continuous batching
@@ -1201,7 +1291,8 @@ class AuroraCapEngine:
 
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
-                       sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None):
+                       sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None,
+                       logit_rules: Optional[dict] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -1226,11 +1317,16 @@ class AuroraCapEngine:
         Same ids either way.  An engine whose only spare sequences are holders must be called with overlap=False: the default
         follows spare_slots.
         logprobs=n: yields (index, dict) - ids, token_logprobs, top_ids, top_logprobs as in `generate` - in both modes, for clips
-        from either front end."""
+        from either front end.
+        logit_rules: one dict for every clip of the call, as in `generate`; a re-filled slot gets its record where it gets its
+        sampling record, before its first token is picked, and its history starts empty."""
         lpn = check_logprobs(logprobs)
         samp = S.check_sampling(sampling)
+        rules = LR.check_logit_rules(logit_rules)
         if samp is not None:
             self._sampling_on()
+        if rules is not None:
+            self._rules_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         B = self.max_batch if slots is None else slots
@@ -1246,7 +1342,7 @@ class AuroraCapEngine:
             if self.spare_slots - n_hold < 1:
                 raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1 beyond its prefix_cache")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph, samp, stream_of, share_key, holders, lpn)
+                                                       front_graph, samp, stream_of, share_key, holders, lpn, rules)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -1272,6 +1368,8 @@ class AuroraCapEngine:
                             self.slot_reset(s)
                             if samp is not None:
                                 self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
+                            if rules is not None:
+                                self.slot_logit_rules(s, LR.records(rules, 1))
                             self.extend_batch(s, 1, buf, fork, stride, new)
                             owner[s] = idx
                             continue
@@ -1281,6 +1379,8 @@ class AuroraCapEngine:
                         self.slot_reset(s)
                         if samp is not None:
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
+                        if rules is not None:
+                            self.slot_logit_rules(s, LR.records(rules, 1))
                         self.prefill(s, emb, L)                   # argument checks come before any enqueue: a rejection leaves the slot idle
                         if key is not None:
                             self._holder_fill(holders, key, s, vis, plan, px, r)
@@ -1393,7 +1493,7 @@ class AuroraCapEngine:
         return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"]), fg
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
-                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None):
+                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None, rules=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -1420,6 +1520,8 @@ class AuroraCapEngine:
                         emb.record_stream(sD)
                         if samp is not None:                      # the captured front end holds the stage only: the pick is the commit's
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
+                        if rules is not None:                     # begin_batch made every slot neutral; a commit keeps a slot's record
+                            self.slot_logit_rules(s, LR.records(rules, 1))
                         if isinstance(L, tuple) and L[0] == "extend":     # a sibling staged behind a copied prefix: (_, fork, stride, rows)
                             L[3].record_stream(sD)
                             self.extend_commit(s, 1, seq, emb, L[1], L[2], L[3])

@@ -19,6 +19,7 @@ from typing import Optional
 import torch
 
 from .engine import AuroraCapEngine
+from .logit_rules import KEYS as LOGIT_RULE_KEYS, check_logit_rules
 from .sampling import DEFAULT_TOP_K, check_sampling
 from .scoring import check_logprobs
 
@@ -57,6 +58,20 @@ def generation_top_k(path: str) -> Optional[int]:
     return None
 
 
+def generation_logit_rules(path: str) -> dict:
+    """The `repetition_penalty` / `no_repeat_ngram_size` / `min_new_tokens` the language model's generation_config.json sets under an
+    xtuner-layout checkpoint directory (found the way `generation_top_k` finds it): only the keys it holds with a value, {} without."""
+    import json
+    import os
+    for sub in ("llm", ""):
+        f = os.path.join(path, sub, "generation_config.json")
+        if os.path.isfile(f):
+            with open(f) as fh:
+                cfg = json.load(fh)
+            return {k: cfg[k] for k in LOGIT_RULE_KEYS if cfg.get(k) is not None}
+    return {}
+
+
 class AuroraEncoder:
     """visual_encoder handle (aurora.py:869-904): only the ratio knob and the r formula live on the host."""
 
@@ -87,12 +102,15 @@ class _LLM:
         self._e = engine
         self.eos_token_id = eos_token_id
         self.generation_top_k = None          # generation_config.json's top_k, when the checkpoint has one (AuroraModel.from_pretrained)
+        self.generation_logit_rules = {}      # its repetition_penalty / no_repeat_ngram_size / min_new_tokens, those it sets
         self.config = engine.l
 
     def generate(self, inputs_embeds: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.0, top_p: float = 1.0,
                  num_beams: int = 1, max_new_tokens: int = 2048, input_ids=None, position_ids=None, attention_mask=None,
                  past_key_values=None, labels=None, eos_token_id="default", top_k="default", seed: int = 0, stream: int = 0,
-                 output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False, **unused):
+                 output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False,
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                 min_new_tokens: Optional[int] = None, **unused):
         """do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
         sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
         passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
@@ -103,7 +121,13 @@ class _LLM:
         return_dict_in_generate=True: a `GenerateOutput` instead of the ids tensor; with output_logprobs=True it carries the
         log-probability of every generated token and its `top_logprobs` (0 .. 8) most likely alternatives, under the model's
         unmodified distribution whatever do_sample says.  output_logprobs=True needs return_dict_in_generate=True (ValueError);
-        `output_scores` stays ignored."""
+        `output_scores` stays ignored.
+        repetition_penalty (1.0 = off), no_repeat_ngram_size (0 = off), min_new_tokens (0 = off): transformers' three logits
+        processors on the raw row ahead of the pick, greedy or sampled (`aurora_amd.logit_rules`).  Their history is the tokens
+        GENERATED so far, not the prompt - what transformers sees here too, since `generate(inputs_embeds=...)` starts `input_ids`
+        empty.  None (the default): the value of the checkpoint's generation_config.json (`self.generation_logit_rules`) when it
+        sets one, else off; an explicit argument wins.  Values transformers rejects raise ValueError.  Log-probabilities stay
+        those of the unmodified row."""
         if output_logprobs and not return_dict_in_generate:
             raise ValueError("output_logprobs=True needs return_dict_in_generate=True (the plain call returns the ids tensor alone)")
         lpn = check_logprobs(top_logprobs) if output_logprobs else None
@@ -116,6 +140,8 @@ class _LLM:
             if top_k == "default":
                 top_k = DEFAULT_TOP_K if self.generation_top_k is None else self.generation_top_k
             sampling = check_sampling(dict(temperature=temperature, top_p=top_p, top_k=top_k, seed=seed))
+        given = dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens)
+        rules = check_logit_rules({k: self.generation_logit_rules.get(k) if v is None else v for k, v in given.items()})
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
             raise ValueError(f"inputs_embeds must be [1, L, {self.config['hidden_size']}], got {tuple(inputs_embeds.shape)}")
         eos = self.eos_token_id if eos_token_id == "default" else eos_token_id
@@ -124,6 +150,8 @@ class _LLM:
         pad[:L] = inputs_embeds[0].to(device=self._e.dev, dtype=torch.float16)
         n = min(max_new_tokens, self._e.max_new_tokens)
         kw = dict(sampling=sampling, streams=[stream]) if sampling else {}
+        if rules is not None:
+            kw["logit_rules"] = rules
         if lpn is None:
             ids = self._e.generate([pad], [L], n, eos_id=eos, **kw)[0]
             seq = torch.tensor([ids], dtype=torch.long)
@@ -149,18 +177,22 @@ class AuroraModel:
                               max_new_tokens=max_new_tokens, **kw)
         model = cls(eng, cfg["llm"].get("eos_token_id", 2), slowfast=slowfast)
         model.llm.generation_top_k = generation_top_k(path)
+        model.llm.generation_logit_rules = generation_logit_rules(path)
         return model
 
     def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None,
-                      logprobs: Optional[int] = None):
+                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
         sampling=dict(temperature, top_k, top_p, seed): sampled captions, clip i drawing with stream streams[i] (default: i).
         share: one hashable key per clip (or None); clips of equal key are the same visual input and share its ViT pass and the KV
         of their common prefix inside a chunk of max_batch clips (AuroraCapEngine.caption_batch).
-        logprobs=n (0 .. 8): a dict per clip instead - ids, token_logprobs, top_ids, top_logprobs (AuroraCapEngine.generate)."""
+        logprobs=n (0 .. 8): a dict per clip instead - ids, token_logprobs, top_ids, top_logprobs (AuroraCapEngine.generate).
+        logit_rules=dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0): the three rules of `llm.generate` for
+        every clip of the call, each over its own generated tokens (not its prompt)."""
         check_logprobs(logprobs)
+        rules = check_logit_rules(logit_rules)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
@@ -173,6 +205,8 @@ class AuroraModel:
                 kw["share"] = list(share)[c0:c0 + len(group)]
             if logprobs is not None:
                 kw["logprobs"] = logprobs
+            if rules is not None:
+                kw["logit_rules"] = rules
             out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 
@@ -187,11 +221,12 @@ class AuroraModel:
                                                self.visual_encoder.visual_token_merge_ratio, share=share)
 
     def caption_prompts(self, pixel_values, list_of_input_ids, max_new_tokens: int = 2048, eos_token_id="default", sampling=None,
-                        streams=None):
+                        streams=None, logit_rules: Optional[dict] = None):
         """One clip, several prompts (the five VDC questions about a video): pixel_values [f, c, h, w], each prompt's input ids with
         -200 markers -> one new-token id list per prompt, in order, each identical to captioning (clip, prompt) alone.  The ViT runs
         once per chunk of max_batch prompts and the later prompts prefill only the rows behind the last visual token.  A slow-fast
-        model never shares: its prompts run one at a time through the three calls."""
+        model never shares: its prompts run one at a time through the three calls.  logit_rules: as in `caption_batch`."""
+        rules = check_logit_rules(logit_rules)
         prompts = [ids.tolist() if torch.is_tensor(ids) else list(ids) for ids in list_of_input_ids]
         if self.slowfast:
             out, ratio = [], self.visual_encoder.visual_token_merge_ratio
@@ -199,27 +234,31 @@ class AuroraModel:
                 self.visual_encoder.reset_tome_r(ratio)                           # the slow-fast forward leaves it at 1.0
                 emb = self.forward({"pixel_values": pixel_values.unsqueeze(0), "input_ids": [ids]}, mode="inference")
                 kw = dict(do_sample=False) if sampling is None else dict(sampling, do_sample=True, stream=k if streams is None else list(streams)[k])
+                kw.update(rules if rules is not None else dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0))
                 out.append(self.llm.generate(**emb, num_beams=1, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, **kw)[0].tolist())
             self.visual_encoder.reset_tome_r(ratio)
             return out
         return self.caption_batch([(pixel_values, ids) for ids in prompts], max_new_tokens, eos_token_id, sampling, streams,
-                                  share=[0] * len(prompts))
+                                  share=[0] * len(prompts), **({} if rules is None else dict(logit_rules=rules)))
 
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
-                       overlap=None, sampling=None, stream_of=None, share_key=None):
+                       overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): yields (index, new-token ids) as captions
         finish (EOS or max_new_tokens), re-filling freed KV slots with the next clips.  Per-clip results equal the
         one-at-a-time calls.  overlap (default: on for an engine with spare KV sequences): the next clips' front ends run
         ahead on a CU-masked stream while the slots decode (AuroraCapEngine.caption_stream).
         sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip k draws with stream stream_of(k) (default: k).
-        share_key: callable index -> key | None; clips of equal key are the same visual input (engine built with prefix_cache >= 1)."""
+        share_key: callable index -> key | None; clips of equal key are the same visual input (engine built with prefix_cache >= 1).
+        logit_rules: as in `caption_batch`; a clip's history starts empty in whatever slot it lands."""
+        rules = check_logit_rules(logit_rules)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         n = min(max_new_tokens, self.engine.max_new_tokens)
         it = ((px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips)
         yield from self.engine.caption_stream(it, self.visual_encoder.visual_token_merge_ratio, n, eos, check_every=check_every,
                                               on_error=on_error, overlap=overlap,
                                               **(dict(share_key=share_key) if share_key is not None else {}),
-                                              **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}))
+                                              **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}),
+                                              **(dict(logit_rules=rules) if rules is not None else {}))
 
     def __call__(self, data: dict, data_samples=None, mode: str = "loss"):
         return self.forward(data, data_samples, mode)

@@ -220,6 +220,24 @@ typedef struct aur_sampling { float temperature, top_p; int32_t top_k; uint32_t 
  * produces the slot's first token.  temperature < 0 (-> 0), top_p outside (0, 1] (<= 0: the maximum alone; > 1: off), top_k < 0
  * (-> off) are clamped by the kernel (the host cannot see them); the Python layer validates where the values are known. */
 int aur_slot_sampling(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_sampling* params_dev, void* stream);
+/* Logit rules ahead of the pick: with option "logit_rules" = 1 (aur_set_option) every prefill / commit / decode
+ * step rewrites the slot's fp32 logits row before the token is picked - greedy or sampled - and puts the model's values back behind the
+ * pick, so aur_copy_logits and the log-probability records keep seeing the unmodified row.  The rules are transformers'
+ * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinNewTokensLengthLogitsProcessor over the history h = the n tokens
+ * the slot has GENERATED so far (not the prompt: generate(inputs_embeds=...) starts input_ids empty):
+ *   repetition_penalty p (1 = off; <= 0 or NaN -> 1): every distinct token t of h, once: l[t] = l[t] < 0 ? l[t] * p : l[t] / p in fp32,
+ *     the divide correctly rounded;
+ *   no_repeat_ngram g (0 = off; < 0 -> 0): if n + 1 >= g, l[h[i + g - 1]] = -inf for every i in [0, n - g + 1) with
+ *     h[i .. i + g - 1) == h[n - g + 1 .. n); g = 1 bans every generated token;
+ *   min_new_tokens m (0 = off; < 0 -> 0): while n < m, l[eos] = -inf; nothing when the batch has no EOS (eos_id < 0).
+ * A ban wins over a penalty on the same index; the result does not depend on the order of the rules.  aurora_amd/logit_rules.py is
+ * the definition in numpy.  reserved: 0. */
+typedef struct aur_logit_rules { float repetition_penalty; int32_t no_repeat_ngram; int32_t min_new_tokens; int32_t reserved; } aur_logit_rules;
+/* per-slot records of the selected bank: aur_slot_sampling's contract - device-to-device from caller-owned DEVICE memory, enqueue-only,
+ * recordable; a capture freezes the pointer, not the values; ordered before the prefill / commit that picks the slot's first token.
+ * aur_begin_batch and aur_slot_reset set the slots they clear to neutral (the all-zero record: a penalty <= 0 counts as 1, like
+ * (1, 0, 0)): such a slot's row is never touched.  A commit keeps a slot's record. */
+int aur_slot_logit_rules(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_logit_rules* rules_dev, void* stream);
 /* Run `steps` decode steps for slots [0, batch): one new token per unfinished slot per step. */
 int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream);
 /* Synchronises the stream and copies results to host: ids [batch * max_new_tokens], lens [batch]. */
@@ -352,6 +370,12 @@ int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream);
  * of the kept set). */
 int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const aur_sampling* params_dev,
                     const int32_t* n_dev, int32_t* tokens_out, int32_t* kept_out, void* stream);
+/* The logit-rule kernels alone on caller rows (parity tests).  logits fp32 [rows, vocab] device, rewritten in place; ids_dev int32
+ * [rows, ids_stride] and lens_dev int32 [rows]: row i's history is ids_dev[i][0 .. min(lens_dev[i], ids_stride)); rules_dev [rows];
+ * eos_id as aur_begin_batch takes it.  restore = 0: the processed rows stay; restore = 1: apply, then restore - every row is bitwise
+ * its input again.  Allocates its side list, synchronises the stream and frees it: not recordable. */
+int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const int32_t* ids_dev, int32_t ids_stride,
+                         const int32_t* lens_dev, const aur_logit_rules* rules_dev, int32_t eos_id, int32_t restore, void* stream);
 
 /* ---- scoring given continuations (lmms-eval's `loglikelihood` request) ---------------------------------------
  * aur_score_rows: the kernel alone on caller rows.  logits fp32 [rows, vocab] device; targets_dev int32 [rows].  Per row, with a =
@@ -418,7 +442,10 @@ int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int3
  * aur_decode_stamps_read), "sampling" 0 (default: the pick is argmax_advance_kernel) / 1 (sample_advance_kernel with the slots'
  * aur_sampling records; the kernel choice is frozen inside captured graphs - the decode step's, which this call drops, and a CALLER's
  * capture that holds a prefill / commit, which the caller re-captures), "sample_stage" 1 (default: the sampler stages its logits
- * row in LDS when it fits) / 0 (re-reads it from L2; same tokens).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
+ * row in LDS when it fits) / 0 (re-reads it from L2; same tokens), "logit_rules" 0 (default: the launches are exactly those of a ctx
+ * that never heard of them) / 1 (logit_rules_apply_kernel ahead of every pick and logit_rules_restore_kernel behind it, with the slots'
+ * aur_logit_rules records; frozen inside captured graphs exactly like "sampling"; the first 1 allocates the banks' side lists -
+ * max_batch * (max_new_tokens + 1) entries of 8 bytes each - which live as long as the ctx).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
  * launch) / 0 (its own launch; bitwise the same); "prefill_prune_last" 1 (default) / 0: the last layer of a prefill computes K / V for
  * every position and the rest for each sequence's last 128 rows only - nothing else is read after it; bitwise the same logits and K / V;
  * "decode_half_grid" 1 / 0 (one graph is kept per setting): the next aur_llm_decode calls go to a stream that owns half of the CUs, so
@@ -434,7 +461,7 @@ int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int3
  * LDS above), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
 int aur_set_option(aur_ctx* ctx, const char* name, int64_t value);
 /* Time one kernel of the LLM path in isolation on the current generation state (after aur_llm_prefill):
- * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), pre_norm, pre_qkv, pre_attn,
+ * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), pre_norm, pre_qkv, pre_attn,
  * pre_o, pre_gateup, pre_down}; mean microseconds per launch over `iters` launches cycling through the layers. */
 int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, double* us_out, void* stream);
 

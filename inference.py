@@ -40,6 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--do_sample', action='store_true', help='seeded sampling with --temperature (required, > 0) / --top_p / --top_k instead of greedy decoding')
     parser.add_argument('--top_k', type=int, default=50, help='with --do_sample: keep the k most likely tokens (0 = off)')
     parser.add_argument('--seed', type=int, default=0, help='with --do_sample: seed of the counter-based generator (same seed, same caption)')
+    # transformers' remedies for loops, ahead of the pick (greedy or sampled); their history is the generated tokens, not the prompt.
+    # Left out, a flag falls back to the checkpoint's generation_config.json, then to off
+    parser.add_argument('--repetition_penalty', type=float, default=None, help='divide (positive) / multiply (negative) the logit of every token generated so far by this (> 0; 1.0 = off)')
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=None, help='no n-gram of this size occurs twice in the generated tokens (0 = off)')
+    parser.add_argument('--min_new_tokens', type=int, default=None, help='the EOS token cannot be picked before this many tokens (0 = off)')
     # more questions about the same input: the vision tower runs once and the later prompts prefill only the rows behind the last visual token
     parser.add_argument('--extra_prompt', action='append', default=[], metavar='TEXT',
                         help='a further instruction about the same visual input (repeatable): one more caption is printed per flag, in order; '
@@ -75,6 +80,12 @@ def main():
         sys.exit("error: --logprobs takes a number of alternatives in [0, 8]")
     if args.logprobs is not None and (args.extra_prompt or args.score is not None):
         sys.exit("error: --logprobs goes with one generated caption (not with --extra_prompt or --score)")
+    rule_args = {k: getattr(args, k) for k in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens") if getattr(args, k) is not None}
+    try:
+        from aurora_amd.logit_rules import check_logit_rules
+        check_logit_rules(rule_args)
+    except ValueError as e:
+        sys.exit(f"error: {e}")
     if args.num_beams != 1:
         sys.exit("error: beam search is not implemented on the MI355X path: generation is greedy or, with --do_sample, sampled (--num_beams 1)")
 
@@ -158,14 +169,15 @@ def main():
     if extra_ids:                     # several prompts about one input: one caption per prompt, in order
         px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
         samp = dict(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=args.seed) if args.do_sample else None
-        outs = model.caption_prompts(px, [data["input_ids"][0].tolist()] + extra_ids, max_new_tokens=args.max_new_tokens, sampling=samp)
+        outs = model.caption_prompts(px, [data["input_ids"][0].tolist()] + extra_ids, max_new_tokens=args.max_new_tokens, sampling=samp,
+                                     **(dict(logit_rules=rule_args) if rule_args else {}))
         for ids in outs:
             print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
         return
     output = model(data, mode="inference")
     sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
     cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
-                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample,
+                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample, **rule_args,
                               **(dict(return_dict_in_generate=True, output_logprobs=True, top_logprobs=args.logprobs)
                                  if args.logprobs is not None else {}))
     lp_out = None
