@@ -161,11 +161,10 @@ static int aur_fail(aur_ctx* ctx, int code, const char* fmt, ...) {
     } while (0)
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-// every GEMM of a ctx goes through here: the ctx's tuning knobs travel in the argument block (no process-global state)
-static hipError_t ctx_gemm(const aur_ctx* ctx, GemmArgs& a, int epi, hipStream_t s);
 static inline int64_t rup64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-static hipError_t ctx_gemm(const aur_ctx* ctx, GemmArgs& a, int epi, hipStream_t s) {
+// every GEMM of a ctx goes through here: the ctx's tuning knobs travel in the argument block (no process-global state)
+static hipError_t ctx_gemm(const aur_ctx* ctx, GemmArgs a, int epi, hipStream_t s) {
     a.gemm_mode = ctx->gemm_mode;
     a.max_wgs = ctx->gemm_max_wgs;
     a.tail_split = ctx->gemm_tail_split;
@@ -853,6 +852,31 @@ extern "C" int aur_tome_step(aur_ctx* ctx, const float* metric, const void* x, c
     return AUR_OK;
 }
 
+// ------------------------------------------------------------------------------------------ skinny-GEMM launches
+// THE structure rule: which skinny-GEMM structure (kernels.h SkinnyArgs: variant, part, row_cnt, gu_ks, half_grid) a launch of `mode`
+// gets on THIS engine - a function of the engine's capacity and its knobs, never of the live batch.  Every SkinnyArgs of the library is
+// built here: the decode step's projections (mk_sk_qkv / _row / _gateup under mk_dec_*), the lm_head (mk_lm_head), aur_microbench and
+// the parity entries (aur_linear_skinny, aur_decode_proj_rows, aur_attn_decode_rows), which differ only in the buffers they pass.
+// tests/skinny_ref.py structure() is the tests' independent statement of the rule.
+// ssq_in != nullptr: the RMSNorm folded into W, 1/rms from the rows' sum(x^2).  part / row_cnt: the split-K partials and arrival
+// counters an SK_ROW launch may take (ignored by the other modes).
+static SkinnyArgs mk_skinny(const aur_ctx* ctx, int mode, const half_t* xf, const half_t* W, int B, int b_lo, int b_hi, int K, int Npad, int n_real,
+                            const unsigned long long* ssq_in, unsigned long long* ssq_zero, float* part, int* row_cnt) {
+    SkinnyArgs a{};
+    a.xf = xf; a.W = W; a.B = B; a.b_lo = b_lo; a.b_hi = b_hi; a.K = K; a.Npad = Npad; a.n_real = n_real; a.mode = mode;
+    a.ssq_in = ssq_in; a.norm_eps = ssq_in ? ctx->cfg.llm_rms_eps : 0.f; a.ssq_zero = ssq_zero;
+    const bool wide = mode == SK_QKV || mode == SK_SILU_MUL;        // N of several tiles per CU: x through LDS at every capacity (derive)
+    a.variant = wide ? ctx->skinny_variant_wide : ctx->skinny_variant;
+    if (mode == SK_LOGITS) return a;                                // the lm_head runs outside the step's half grid
+    a.half_grid = ctx->decode_half;
+    if (mode == SK_ROW) {
+        a.part = (K >= ctx->row_split_min_k || ctx->cfg.max_batch > 64) ? part : nullptr;
+        a.row_cnt = ctx->fused_reduce ? row_cnt : nullptr;
+    }
+    if (mode == SK_SILU_MUL) a.gu_ks = ctx->cfg.max_batch > 64 ? 1 : 2;
+    return a;
+}
+
 // ------------------------------------------------------------------------------------------ generic ops
 extern "C" int aur_linear(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad, int32_t n,
                           const float* bias, int32_t act, const void* resid, void* c, void* stream) {
@@ -872,9 +896,8 @@ extern "C" int aur_linear_skinny(aur_ctx* ctx, const void* a, int32_t m, int32_t
     hipStream_t st = (hipStream_t)stream;
     CK(hipMemsetAsync(ctx->d_scr, 0, (size_t)AUR_MAX_BATCH * 16384 * 2, st));
     CK(launch_xfrag_pack((const half_t*)a, k, m, k, ctx->d_scr, st));
-    SkinnyArgs s{};
-    s.xf = ctx->d_scr; s.W = (const half_t*)w_packed; s.B = m; s.b_lo = 0; s.b_hi = m; s.Npad = npad; s.K = k; s.n_real = n;
-    s.mode = SK_LOGITS; s.out32 = out; s.variant = ctx->skinny_variant;
+    SkinnyArgs s = mk_skinny(ctx, SK_LOGITS, ctx->d_scr, (const half_t*)w_packed, m, 0, m, k, npad, n, nullptr, nullptr, nullptr, nullptr);
+    s.out32 = out;
     CK(launch_skinny(s, st));
     return AUR_OK;
 }
@@ -951,6 +974,68 @@ static KvLayout llm_kv(const aur_ctx* c, int layer) {
     return L;
 }
 
+// ---- one builder per decode launch: the caller passes the buffers that differ, the structure comes from mk_skinny.  The decode step
+// (mk_dec_*, also timed by aur_microbench) passes the bank's buffers, the parity entries the caller's scratch.
+static SkinnyArgs mk_sk_qkv(const aur_ctx* ctx, int l, const half_t* xf, const half_t* W, int B, int K, const float2* rope, const int32_t* pos,
+                            const unsigned long long* ssq_in, unsigned long long* ssq_zero) {
+    const int d = ctx->cfg.llm_hidden;
+    SkinnyArgs q = mk_skinny(ctx, SK_QKV, xf, W, B, 0, B, K, ctx->l_qkv_npad, 3 * d, ssq_in, ssq_zero, nullptr, nullptr);
+    q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.qbuf = ctx->d_q; q.kv = llm_kv(ctx, l); q.rope = rope; q.pos = pos; q.seq_ids = nullptr;
+    return q;
+}
+// residual projection (o, down): xres += W x, sum(xres^2) added to ssq_out
+static SkinnyArgs mk_sk_row(const aur_ctx* ctx, const half_t* xf, const half_t* W, half_t* xres, unsigned long long* ssq_out, float* part, int* row_cnt,
+                            int B, int b_lo, int b_hi, int K, int Npad, int n_real) {
+    SkinnyArgs a = mk_skinny(ctx, SK_ROW, xf, W, B, b_lo, b_hi, K, Npad, n_real, nullptr, nullptr, part, row_cnt);
+    a.xres = xres; a.ssq_out = ssq_out;
+    return a;
+}
+// gate/up: out_f = SiLU(gate) * up, n_real / 2 columns in x-fragment form
+static SkinnyArgs mk_sk_gateup(const aur_ctx* ctx, const half_t* xf, const half_t* W, half_t* out_f, int B, int b_lo, int b_hi, int K, int Npad,
+                               int n_real, const unsigned long long* ssq_in, unsigned long long* ssq_zero) {
+    SkinnyArgs a = mk_skinny(ctx, SK_SILU_MUL, xf, W, B, b_lo, b_hi, K, Npad, n_real, ssq_in, ssq_zero, nullptr, nullptr);
+    a.out_f = out_f; a.out_k32 = n_real / 64;
+    return a;
+}
+// the lm_head on batch columns [b_lo, b_hi) of B: the final RMSNorm is folded into its weight, 1/rms from ssq_in
+static SkinnyArgs mk_lm_head(const aur_ctx* ctx, const half_t* xf, const unsigned long long* ssq_in, float* out32, int B, int b_lo, int b_hi) {
+    SkinnyArgs h = mk_skinny(ctx, SK_LOGITS, xf, ctx->l_head_w, B, b_lo, b_hi, ctx->cfg.llm_hidden, ctx->l_vocab_pad, ctx->cfg.llm_vocab, ssq_in, nullptr,
+                             nullptr, nullptr);
+    h.out32 = out32;
+    return h;
+}
+
+static SkinnyArgs mk_dec_qkv(aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
+    return mk_sk_qkv(ctx, l, K.d_x, ctx->ll[l].qkv_w, K.batch, ctx->cfg.llm_hidden, ctx->l_rope, K.s_pos, K.s_ssq_mlp, K.s_ssq_attn);
+}
+static DecAttnArgs mk_dec_attn(aur_ctx* ctx, int l) {
+    const aur_config& g = ctx->cfg;
+    DecAttnArgs at{};
+    at.qbuf = ctx->d_q; at.kv = llm_kv(ctx, l); at.pos = ctx->bank().s_pos; at.seq_ids = nullptr; at.B = ctx->bank().batch; at.heads = g.llm_heads;
+    at.hd = ctx->l_hd; at.nsplit = ctx->nsplit; at.pages_per_split = ctx->pps; at.scale = 1.0f / sqrtf((float)ctx->l_hd);
+    at.part_o = ctx->d_part_o; at.part_ml = ctx->d_part_ml; at.out_f = ctx->d_attn; at.out_k32 = g.llm_hidden / 32;
+    // engines whose capacity alone gives one attention workgroup per CU and still split the context (8-15 slots of 32 heads): the splits of a
+    // (sequence, head) are the waves of one workgroup and meet in LDS - bitwise the two-launch result, one launch per layer less
+    at.local_splits = (g.max_batch * g.llm_heads >= gemm256_grid_cap() /* one attention workgroup per CU */ && (ctx->nsplit == 2 || ctx->nsplit == 4) && ctx->l_hd == 128 && ctx->attn_local) ? ctx->nsplit : 0;
+    return at;
+}
+static SkinnyArgs mk_dec_o(aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
+    const int d = ctx->cfg.llm_hidden;
+    return mk_sk_row(ctx, ctx->d_attn, ctx->ll[l].o_w, K.d_x, K.s_ssq_attn, ctx->d_part_row, ctx->d_row_cnt, K.batch, 0, K.batch, d, ctx->l_dpad, d);
+}
+static SkinnyArgs mk_dec_gateup(aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
+    return mk_sk_gateup(ctx, K.d_x, ctx->ll[l].gateup_w, ctx->d_h, K.batch, 0, K.batch, ctx->cfg.llm_hidden, ctx->l_gu_npad, 2 * ctx->cfg.llm_mlp,
+                        K.s_ssq_attn, K.s_ssq_mlp);
+}
+static SkinnyArgs mk_dec_down(aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
+    return mk_sk_row(ctx, ctx->d_h, ctx->ll[l].down_w, K.d_x, K.s_ssq_mlp, ctx->d_part_row, ctx->d_row_cnt, K.batch, 0, K.batch, ctx->cfg.llm_mlp,
+                     ctx->l_dpad, ctx->cfg.llm_hidden);
+}
+
 // slots [b0, b0 + nb) of bank K hold no log-probability record: wherever their s_len is zeroed
 static int logprob_clear(aur_ctx* ctx, const aur_ctx::Bank& K, int b0, int nb, hipStream_t s) {
     if (K.lp_len) CK(launch_token_logprob_clear(b0, nb, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id, K.lp_top_lp, s));
@@ -990,11 +1075,7 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
                                int len_cap = 0) {
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
-    SkinnyArgs h{};
-    h.xf = K.d_x; h.W = ctx->l_head_w; h.B = K.batch; h.Npad = ctx->l_vocab_pad; h.K = g.llm_hidden; h.n_real = g.llm_vocab;
-    h.mode = SK_LOGITS; h.out32 = K.d_logits; h.b_lo = b0; h.b_hi = b0 + nb; h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
-    h.variant = ctx->skinny_variant;
-    CK(launch_skinny(h, s));
+    CK(launch_skinny(mk_lm_head(ctx, K.d_x, K.s_ssq_mlp, K.d_logits, K.batch, b0, b0 + nb), s));
     // logit rules: the affected entries of the rows are rewritten for the pick alone; behind it the rows are the model's again
     if (ctx->logit_rules)
         CK(launch_logit_rules_apply(K.d_logits, b0, nb, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
@@ -1012,51 +1093,85 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     return AUR_OK;
 }
 
+// ---- one description of a prefill pass: nseq sequences into KV sequences [seq0, seq0 + nseq), rows in x [nseq * rows_per_seq(), d].
+// Three forms, told apart by check_pass and by nothing else:
+//   fixed length (aur_llm_prefill*):      lens == nullptr, pos0 == 0 - every sequence holds t rows, rup(t, 32) rows apart.
+//   variable (aur_llm_prefill_*_var):     lens != nullptr, pos0 == 0 - t is the row stride, a multiple of 32, and sequence i holds lens[i] rows
+//       (device memory, never read on the host: enqueue-only, capturable); the attention kernel reads the lengths, the other kernels of a
+//       layer work row by row and need none.
+//   extend (aur_llm_extend_*_var):        lens != nullptr, pos0 > 0 - the rows are positions [pos0, pos0 + lens[i]) of sequences whose pages
+//       already hold [0, pos0): RoPE and the page write at pos0 + row, queries at pos0 + row over keys [0, pos0 + lens[i]); everything else
+//       is the same launch.
+struct PrefillPass {
+    int seq0, nseq;
+    half_t* x;
+    int t;                       // seq_len, or the stride
+    const int32_t* lens;
+    int pos0;
+    bool prune_ok;               // false (aur_llm_score_var): the last layer runs over every row - rows in front of the last 128 are read after it
+    int rows_per_seq() const { return rup(t, 32); }
+    // first element in x of sequence 0's last prompt row: t - 1 by value, or found per sequence from the device lengths (launch_xfrag_norm)
+    int64_t last_row(int d) const { return lens ? 0 : (int64_t)(t - 1) * d; }
+    // decode position behind the pass, as lm_head_and_advance's (set_pos, lens, len_cap = rows_per_seq()): t, or pos0 + lens[i] on the device
+    int set_pos() const { return lens ? pos0 : t; }
+    // RoPE position of the first row of the pruned last layer's 128-row tail block: row0 by value, or pos0 + the row0 the query GEMM derives
+    // per sequence from the device lengths (GemmArgs.tail_lens)
+    int tail_rope_pos0(int row0) const { return lens ? pos0 : pos0 + row0; }
+};
+
+// ---- the four GEMMs of a prefill layer on M rows of A (all rows of a pass, or the compact 128-row tails of its last layer)
+enum { QKV_Q = 1, QKV_KV = 2, QKV_ALL = 3 };     // column blocks of the packed QKV weight: the Q third's tiles come first
+static GemmArgs mk_pre_qkv(const aur_ctx* ctx, int l, const half_t* A, int M, int rows_per_seq, int seq0, int pos0, int cols, int tag) {
+    const int d = ctx->cfg.llm_hidden;
+    GemmArgs q{};
+    q.A = A; q.lda = d; q.W = ctx->ll[l].qkv_w + ((cols & QKV_Q) ? 0 : (int64_t)(d / 16) * (d / 32) * AUR_FRAG_HALVES); q.M = M; q.K = d;
+    q.Npad = cols == QKV_ALL ? ctx->l_qkv_npad : cols == QKV_Q ? d : ctx->l_qkv_npad - d;
+    q.rows_per_seq = rows_per_seq; q.q_cols = (cols & QKV_Q) ? d : 0; q.k_cols = (cols & QKV_KV) ? d : 0; q.hd = ctx->l_hd; q.Qf = ctx->l_qf;
+    q.kv = llm_kv(ctx, l); q.rope = ctx->l_rope; q.pos0 = pos0; q.seq0 = seq0; q.tag = tag;
+    return q;
+}
+static GemmArgs mk_pre_o(const aur_ctx* ctx, int l, const half_t* A, int M, half_t* x, int tag) {
+    const int d = ctx->cfg.llm_hidden;
+    GemmArgs o{};
+    o.A = A; o.lda = d; o.W = ctx->ll[l].o_w; o.M = M; o.Npad = ctx->l_dpad; o.K = d; o.C = x; o.ldc = d; o.resid = x; o.ldr = d;
+    o.n_real = d; o.act = ACT_NONE; o.tag = tag;
+    return o;
+}
+static GemmArgs mk_pre_gateup(const aur_ctx* ctx, int l, const half_t* A, int M, half_t* h, int tag) {
+    const int d = ctx->cfg.llm_hidden, mlp = ctx->cfg.llm_mlp;
+    GemmArgs gu{};
+    gu.A = A; gu.lda = d; gu.W = ctx->ll[l].gateup_w; gu.M = M; gu.Npad = ctx->l_gu_npad; gu.K = d; gu.C = h; gu.ldc = mlp;
+    gu.n_real = 2 * mlp; gu.act = ACT_SILU_MUL; gu.tag = tag;
+    return gu;
+}
+static GemmArgs mk_pre_down(const aur_ctx* ctx, int l, const half_t* A, int M, half_t* x, int tag) {
+    const int d = ctx->cfg.llm_hidden, mlp = ctx->cfg.llm_mlp;
+    GemmArgs dn{};
+    dn.A = A; dn.lda = mlp; dn.W = ctx->ll[l].down_w; dn.M = M; dn.Npad = ctx->l_dpad; dn.K = mlp; dn.C = x; dn.ldc = d;
+    dn.resid = x; dn.ldr = d; dn.n_real = d; dn.act = ACT_NONE; dn.tag = tag;
+    return dn;
+}
+// causal attention of a pass over query rows `rows_per_seq` apart (all rows, or the tail blocks) into O
+static AttnArgs mk_pre_attn(const aur_ctx* ctx, int l, const PrefillPass& p, int rows_per_seq, half_t* O) {
+    AttnArgs at{};
+    at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = p.seq0; at.nseq = p.nseq; at.heads = ctx->cfg.llm_heads; at.rows_per_seq = rows_per_seq;
+    at.t = p.t; at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = O; at.ldo = ctx->cfg.llm_hidden; at.hd = ctx->l_hd;
+    at.seq_lens = p.lens; at.len_cap = p.rows_per_seq(); at.q_pos0 = p.pos0; at.len_pos0 = p.pos0;
+    return at;
+}
+
 // One prefill layer; `which` selects the kernels (bit 0 norm1, 1 qkv, 2 attention, 3 o_proj, 4 norm2, 5 gate/up, 6 down)
 // so that aur_microbench can time each of them in isolation.
-// lens != nullptr (the _var entry points): `seq_len` is the row stride of the sequences, a multiple of 32, and sequence i holds
-// lens[i] rows (device memory, read by the attention kernel); the other kernels of a layer work row by row and need no length.
-// pos0 > 0 (aur_llm_extend_*): the rows are positions [pos0, pos0 + lens[i]) of sequences whose pages already hold [0, pos0) - RoPE and the
-// page write at pos0 + row, queries at pos0 + row over keys [0, pos0 + lens[i]); everything else is the same launch.
-static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr,
-                         int pos0 = 0) {
+static int prefill_layer(aur_ctx* ctx, int l, int which, const PrefillPass& p, hipStream_t s) {
     const aur_config& g = ctx->cfg;
-    const LlmLayerW& w = ctx->ll[l];
-    const int d = g.llm_hidden, Mseq = rup(seq_len, 32), M = nseq * Mseq;
-    if (which & 1) CK(launch_rmsnorm(x, d, nullptr, g.llm_rms_eps, M, d, ctx->l_xn, d, s));      // weight folded into qkv.w
-    if (which & 2) {
-        GemmArgs q{};
-        q.A = ctx->l_xn; q.lda = d; q.W = w.qkv_w; q.bias = nullptr; q.M = M; q.Npad = ctx->l_qkv_npad; q.K = d;
-        q.rows_per_seq = Mseq; q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = pos0; q.seq0 = slot; q.tag = GT_LLM_QKV;
-        CK(ctx_gemm(ctx, q, EPI_QKV, s));
-    }
-    if (which & 4) {
-        AttnArgs at{};
-        at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = Mseq; at.t = seq_len;
-        at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = ctx->l_attn; at.ldo = d; at.hd = ctx->l_hd;
-        at.seq_lens = lens; at.len_cap = Mseq; at.q_pos0 = pos0; at.len_pos0 = pos0;
-        CK(launch_attention(at, s));
-    }
-    if (which & 8) {
-        GemmArgs o{};
-        o.A = ctx->l_attn; o.lda = d; o.W = w.o_w; o.M = M; o.Npad = ctx->l_dpad; o.K = d; o.C = x; o.ldc = d; o.resid = x; o.ldr = d;
-        o.n_real = d; o.act = ACT_NONE; o.tag = GT_LLM_O;
-        CK(ctx_gemm(ctx, o, EPI_ROW, s));
-    }
-    if (which & 16) CK(launch_rmsnorm(x, d, nullptr, g.llm_rms_eps, M, d, ctx->l_xn, d, s));     // weight folded into gateup.w
-    if (which & 32) {
-        GemmArgs gu{};
-        gu.A = ctx->l_xn; gu.lda = d; gu.W = w.gateup_w; gu.M = M; gu.Npad = ctx->l_gu_npad; gu.K = d; gu.C = ctx->l_h; gu.ldc = g.llm_mlp;
-        gu.n_real = 2 * g.llm_mlp; gu.act = ACT_SILU_MUL; gu.tag = GT_LLM_GATEUP;
-        CK(ctx_gemm(ctx, gu, EPI_ROW, s));
-    }
-    if (which & 64) {
-        GemmArgs dn{};
-        dn.A = ctx->l_h; dn.lda = g.llm_mlp; dn.W = w.down_w; dn.M = M; dn.Npad = ctx->l_dpad; dn.K = g.llm_mlp; dn.C = x; dn.ldc = d;
-        dn.resid = x; dn.ldr = d; dn.n_real = d; dn.act = ACT_NONE; dn.tag = GT_LLM_DOWN;
-        CK(ctx_gemm(ctx, dn, EPI_ROW, s));
-    }
+    const int d = g.llm_hidden, Mseq = p.rows_per_seq(), M = p.nseq * Mseq;
+    if (which & 1) CK(launch_rmsnorm(p.x, d, nullptr, g.llm_rms_eps, M, d, ctx->l_xn, d, s));      // weight folded into qkv.w
+    if (which & 2) CK(ctx_gemm(ctx, mk_pre_qkv(ctx, l, ctx->l_xn, M, Mseq, p.seq0, p.pos0, QKV_ALL, GT_LLM_QKV), EPI_QKV, s));
+    if (which & 4) CK(launch_attention(mk_pre_attn(ctx, l, p, Mseq, ctx->l_attn), s));
+    if (which & 8) CK(ctx_gemm(ctx, mk_pre_o(ctx, l, ctx->l_attn, M, p.x, GT_LLM_O), EPI_ROW, s));
+    if (which & 16) CK(launch_rmsnorm(p.x, d, nullptr, g.llm_rms_eps, M, d, ctx->l_xn, d, s));     // weight folded into gateup.w
+    if (which & 32) CK(ctx_gemm(ctx, mk_pre_gateup(ctx, l, ctx->l_xn, M, ctx->l_h, GT_LLM_GATEUP), EPI_ROW, s));
+    if (which & 64) CK(ctx_gemm(ctx, mk_pre_down(ctx, l, ctx->l_h, M, p.x, GT_LLM_DOWN), EPI_ROW, s));
     return AUR_OK;
 }
 
@@ -1067,137 +1182,70 @@ static int prefill_layer(aur_ctx* ctx, int l, int which, int slot, int nseq, hal
 // and throws them away; every value that is kept is bit-identical here - a GEMM's per-element k order does not depend on M, the tile
 // kernels agree bitwise (tests), and the query block sees the same keys.  Saves 83 % of one layer of 32: ~2.5 % of a prefill.
 // Scratch: the compact [nseq * 128] activations live in l_h (free until this layer's gate/up), the compact Q fragments in l_qf.
-// lens != nullptr: the block of sequence i is the 128 rows that end at rup(lens[i], 32) - row0 is per sequence, so the gathers and the
+// p.lens != nullptr: the block of sequence i is the 128 rows that end at rup(lens[i], 32) - row0 is per sequence, so the gathers and the
 // scatter are one small kernel that reads the lengths, and the query GEMM's RoPE position and the attention's q_pos0 derive from them
 // on the device (GemmArgs.tail_lens, AttnArgs.q_tail).  A sequence of <= 128 rows has row0 = 0: its block is the unpruned computation.
-// pos0 > 0 (aur_llm_extend_*): row0 stays relative to the rows of this pass; positions are pos0 + row as in prefill_layer.
-static int prefill_last_layer(aur_ctx* ctx, int l, int slot, int nseq, half_t* x, int seq_len, hipStream_t s, const int32_t* lens = nullptr,
-                              int pos0 = 0) {
+// p.pos0 > 0: row0 stays relative to the rows of this pass; positions are pos0 + row as in prefill_layer.
+static int prefill_last_layer(aur_ctx* ctx, int l, const PrefillPass& p, hipStream_t s) {
     const aur_config& g = ctx->cfg;
-    const LlmLayerW& w = ctx->ll[l];
-    const int d = g.llm_hidden, mlp = g.llm_mlp, Mseq = rup(seq_len, 32), M = nseq * Mseq, LB = 128, Mc = nseq * LB, row0 = Mseq - LB;
+    const int d = g.llm_hidden, nseq = p.nseq, Mseq = p.rows_per_seq(), M = nseq * Mseq, LB = 128, Mc = nseq * LB, row0 = Mseq - LB;
+    half_t* const x = p.x;
     half_t* xn_c = ctx->l_h;
     half_t* attn_c = xn_c + (int64_t)Mc * d;
     half_t* x_c = attn_c + (int64_t)Mc * d;
     half_t* h_c = x_c + (int64_t)Mc * d;
     const size_t rowb = (size_t)d * 2;
     CK(launch_rmsnorm(x, d, nullptr, g.llm_rms_eps, M, d, ctx->l_xn, d, s));
-    {   // K and V of every position (the Q third of the packed weight is skipped: its tiles come first)
-        GemmArgs q{};
-        q.A = ctx->l_xn; q.lda = d; q.W = w.qkv_w + (int64_t)(d / 16) * (d / 32) * AUR_FRAG_HALVES; q.M = M; q.Npad = ctx->l_qkv_npad - d; q.K = d;
-        q.rows_per_seq = Mseq; q.q_cols = 0; q.k_cols = d; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = pos0; q.seq0 = slot; q.tag = GT_LLM_QKV;
-        CK(ctx_gemm(ctx, q, EPI_QKV, s));
-    }
-    if (lens) CK(launch_tail_rows(ctx->l_xn, x, xn_c, x_c, d, nseq, Mseq, LB, lens, 1, s));
+    CK(ctx_gemm(ctx, mk_pre_qkv(ctx, l, ctx->l_xn, M, Mseq, p.seq0, p.pos0, QKV_KV, GT_LLM_QKV), EPI_QKV, s));      // K and V of every position
+    if (p.lens) CK(launch_tail_rows(ctx->l_xn, x, xn_c, x_c, d, nseq, Mseq, LB, p.lens, 1, s));
     else {
         CK(hipMemcpy2DAsync(xn_c, LB * rowb, ctx->l_xn + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
         CK(hipMemcpy2DAsync(x_c, LB * rowb, x + (int64_t)row0 * d, Mseq * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
     }
-    {   // queries of the last block
-        GemmArgs q{};
-        q.A = xn_c; q.lda = d; q.W = w.qkv_w; q.M = Mc; q.Npad = d; q.K = d;
-        q.rows_per_seq = LB; q.q_cols = d; q.k_cols = 0; q.hd = ctx->l_hd; q.Qf = ctx->l_qf; q.kv = llm_kv(ctx, l);
-        q.rope = ctx->l_rope; q.pos0 = lens ? pos0 : pos0 + row0; q.seq0 = slot; q.tag = GT_OTHER; q.tail_lens = lens; q.tail_cap = Mseq;
-        CK(ctx_gemm(ctx, q, EPI_QKV, s));
-    }
-    {
-        AttnArgs at{};
-        at.Qf = ctx->l_qf; at.kv = llm_kv(ctx, l); at.seq0 = slot; at.nseq = nseq; at.heads = g.llm_heads; at.rows_per_seq = LB; at.t = seq_len;
-        at.causal = 1; at.scale = 1.0f / sqrtf((float)ctx->l_hd); at.O = attn_c; at.ldo = d; at.hd = ctx->l_hd; at.q_pos0 = pos0 + row0;
-        at.seq_lens = lens; at.len_cap = Mseq; at.q_tail = 1; at.len_pos0 = pos0;
-        CK(launch_attention(at, s));
-    }
-    {
-        GemmArgs o{};
-        o.A = attn_c; o.lda = d; o.W = w.o_w; o.M = Mc; o.Npad = ctx->l_dpad; o.K = d; o.C = x_c; o.ldc = d; o.resid = x_c; o.ldr = d;
-        o.n_real = d; o.act = ACT_NONE; o.tag = GT_OTHER;
-        CK(ctx_gemm(ctx, o, EPI_ROW, s));
-    }
+    GemmArgs a = mk_pre_qkv(ctx, l, xn_c, Mc, LB, p.seq0, p.tail_rope_pos0(row0), QKV_Q, GT_OTHER);                               // queries of the last block
+    a.tail_lens = p.lens; a.tail_cap = Mseq;
+    CK(ctx_gemm(ctx, a, EPI_QKV, s));
+    AttnArgs at = mk_pre_attn(ctx, l, p, LB, attn_c);
+    at.q_pos0 = p.pos0 + row0; at.q_tail = 1;
+    CK(launch_attention(at, s));
+    CK(ctx_gemm(ctx, mk_pre_o(ctx, l, attn_c, Mc, x_c, GT_OTHER), EPI_ROW, s));
     CK(launch_rmsnorm(x_c, d, nullptr, g.llm_rms_eps, Mc, d, xn_c, d, s));
-    {
-        GemmArgs gu{};
-        gu.A = xn_c; gu.lda = d; gu.W = w.gateup_w; gu.M = Mc; gu.Npad = ctx->l_gu_npad; gu.K = d; gu.C = h_c; gu.ldc = mlp;
-        gu.n_real = 2 * mlp; gu.act = ACT_SILU_MUL; gu.tag = GT_OTHER;
-        CK(ctx_gemm(ctx, gu, EPI_ROW, s));
-    }
-    {
-        GemmArgs dn{};
-        dn.A = h_c; dn.lda = mlp; dn.W = w.down_w; dn.M = Mc; dn.Npad = ctx->l_dpad; dn.K = mlp; dn.C = x_c; dn.ldc = d;
-        dn.resid = x_c; dn.ldr = d; dn.n_real = d; dn.act = ACT_NONE; dn.tag = GT_OTHER;
-        CK(ctx_gemm(ctx, dn, EPI_ROW, s));
-    }
-    if (lens) CK(launch_tail_rows(nullptr, x, nullptr, x_c, d, nseq, Mseq, LB, lens, 0, s));
+    CK(ctx_gemm(ctx, mk_pre_gateup(ctx, l, xn_c, Mc, h_c, GT_OTHER), EPI_ROW, s));
+    CK(ctx_gemm(ctx, mk_pre_down(ctx, l, h_c, Mc, x_c, GT_OTHER), EPI_ROW, s));
+    if (p.lens) CK(launch_tail_rows(nullptr, x, nullptr, x_c, d, nseq, Mseq, LB, p.lens, 0, s));
     else CK(hipMemcpy2DAsync(x + (int64_t)row0 * d, Mseq * rowb, x_c, LB * rowb, LB * rowb, nseq, hipMemcpyDeviceToDevice, s));
     return AUR_OK;
 }
 
-// ---- variable-length forms: sequences `stride` rows apart, lengths in device memory (never read here: enqueue-only, capturable)
-static int var_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds, int stride, const int32_t* lens) {
-    if (!embeds || !lens) return aur_fail(ctx, AUR_ERR_ARG, "%s: null %s", who, !embeds ? "embeds" : "seq_lens_dev");
-    if (stride < 32 || stride % 32) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d is not a positive multiple of 32", who, stride);
-    if (stride > ctx->l_ctx_pad) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d exceeds the %d positions of a sequence's KV pages", who, stride, ctx->l_ctx_pad);
-    if (nseq > ctx->cfg.max_batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: %d sequences exceed the front-end scratch of max_batch %d", who, nseq, ctx->cfg.max_batch);
-    return AUR_OK;
-}
-
-// The layer stack of a prefill pass over KV sequences [seq0, seq0 + nseq): KV pages and front-end scratch only - no decode state.
-// lens != nullptr: seq_len is the stride (checked by var_args) and the rows [lens[i], stride) of every sequence are cleared first: whatever
-// the caller left there, they are zeros in every layer (an all-zero row stays zero through norm, projections, RoPE and the MLP, and the
-// attention kernel stores zeros for it), and so are the K / V written for them.
-// prune = false (aur_llm_score_var): the last layer runs over every row like the others - rows in front of the last 128 are read after it.
-static int prefill_layers(aur_ctx* ctx, int seq0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* who, const int32_t* lens = nullptr,
-                          int pos0 = 0, bool prune_ok = true) {
-    if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
+// The layer stack of a pass: KV pages and front-end scratch only - no decode state.  Opens the "prefill" stage; the tail closes it.
+// p.lens != nullptr: the rows [lens[i], stride) of every sequence are cleared first: whatever the caller left there, they are zeros in
+// every layer (an all-zero row stays zero through norm, projections, RoPE and the MLP, and the attention kernel stores zeros for it), and
+// so are the K / V written for them.
+static int prefill_layers(aur_ctx* ctx, const PrefillPass& p, hipStream_t s) {
     const aur_config& g = ctx->cfg;
-    const aur_ctx::Bank& K = ctx->bank();
-    if (K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
-    if (!lens && (seq_len < 1 || seq_len + K.max_new > g.max_ctx)) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, g.max_ctx);
     stage_begin(ctx, "prefill", s);
-    ctx->last_prefill_len = seq_len;
-    const int Mseq = rup(seq_len, 32);
-    if (lens) CK(launch_clear_tail_rows((half_t*)embeds, g.llm_hidden, nseq, Mseq, lens, s));
+    ctx->last_prefill_len = p.t;
+    const int Mseq = p.rows_per_seq();
+    if (p.lens) CK(launch_clear_tail_rows(p.x, g.llm_hidden, p.nseq, Mseq, p.lens, s));
     for (int l = 0; l < g.llm_layers; ++l) {
         // the compact scratch of the pruned last layer must fit l_h: nseq * 128 * (3 d + mlp) <= nseq * Mseq * mlp (and LB < Mseq)
-        const bool prune = prune_ok && ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
-        int rc = prune ? prefill_last_layer(ctx, l, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0)
-                       : prefill_layer(ctx, l, 0x7f, seq0, nseq, (half_t*)embeds, seq_len, s, lens, pos0);
-        if (rc) return rc;
+        const bool prune = p.prune_ok && ctx->prune_last && l == g.llm_layers - 1 && (int64_t)128 * (3 * g.llm_hidden + g.llm_mlp) <= (int64_t)Mseq * g.llm_mlp && Mseq > 128;
+        if (int rc = prune ? prefill_last_layer(ctx, l, p, s) : prefill_layer(ctx, l, 0x7f, p, s)) return rc;
     }
     return AUR_OK;
 }
-// First tokens of slots [slot0, slot0 + nseq) from the last prompt rows of `embeds` (the final hidden states `prefill_layers` left
-// there): residual fragments + sum(x^2) - the lm_head applies the (folded) final RMSNorm itself -, logits, argmax, bookkeeping.
-static int prefill_first_tokens(aur_ctx* ctx, int slot0, int nseq, void* embeds, int seq_len, hipStream_t s, const char* stage = "prefill",
-                                const int32_t* lens = nullptr, int pos0 = 0) {
+// First tokens of slots [slot0, slot0 + p.nseq) from the last prompt rows of p.x (the final hidden states `prefill_layers` left
+// there): residual fragments + sum(x^2) - the lm_head applies the (folded) final RMSNorm itself -, logits, the pick, bookkeeping.
+static int prefill_first_tokens(aur_ctx* ctx, int slot0, const PrefillPass& p, const char* stage, hipStream_t s) {
     const aur_config& g = ctx->cfg;
-    const int d = g.llm_hidden, Mseq = rup(seq_len, 32);
+    const int d = g.llm_hidden, Mseq = p.rows_per_seq();
     if (ctx->prof) kev_begin(ctx->kev[3], s);
-    // the last prompt row of every sequence and its decode position: seq_len - 1 / seq_len, or per sequence from the device lengths
-    CK(launch_xfrag_norm((half_t*)embeds + (lens ? 0 : (int64_t)(seq_len - 1) * d), (int64_t)Mseq * d, nullptr, g.llm_rms_eps, nseq, d, slot0, ctx->bank().d_x,
-                         ctx->bank().s_ssq_mlp, s, 16, lens, Mseq));
-    int rc = lm_head_and_advance(ctx, slot0, nseq, 0, lens ? pos0 : seq_len, s, lens, Mseq);      // decode position: seq_len, or pos0 + len_i
+    CK(launch_xfrag_norm(p.x + p.last_row(d), (int64_t)Mseq * d, nullptr, g.llm_rms_eps, p.nseq, d, slot0, ctx->bank().d_x, ctx->bank().s_ssq_mlp, s, 16,
+                         p.lens, Mseq));
+    int rc = lm_head_and_advance(ctx, slot0, p.nseq, 0, p.set_pos(), s, p.lens, Mseq);
     if (ctx->prof) kev_end(ctx->kev[3], s);       // closed on the error path too: the event ring and the roctx nesting stay balanced
     stage_end(ctx, stage, s);
     return rc;
-}
-
-extern "C" int aur_llm_prefill_batch(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t seq_len, void* stream) {
-    const int B = ctx->bank().batch;
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = prefill_layers(ctx, slot0, nseq, embeds, seq_len, s, "aur_llm_prefill")) return rc;
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s);
-}
-
-extern "C" int aur_llm_prefill_stage(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t seq_len, void* stream) {
-    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
-        return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_stage: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", seq0, seq0 + nseq, ctx->kv_seqs);
-    // its own timer interval, opened and closed on THIS stream; the commit (decode stream, possibly several stages later) is timed
-    // as "prefill_commit"
-    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, seq_len, (hipStream_t)stream, "aur_llm_prefill_stage")) return rc;
-    stage_end(ctx, "prefill", (hipStream_t)stream);
-    return AUR_OK;
 }
 
 // page-table rows of sequences [a0, a0 + n) <-> [b0, b0 + n)
@@ -1212,18 +1260,57 @@ __global__ void ptab_swap_kernel(int32_t* __restrict__ pt, int a0, int b0, int n
     *pb = t;
 }
 
-static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream, const int32_t* lens,
-                          int pos0 = 0) {
+// ---- the argument checks of every prefill / extend / score entry point, in ONE order: state (finalized, language weights, active batch),
+// range (SLOTS: slots [slot0 ..) inside the active batch; SEQS: sequences [seq0 ..) inside the bank's KV sequences; both for a commit,
+// whose staged sequences are the slots' own or apart from them), then what the form can see of its rows on the host - FIXED: embeds,
+// seq_len >= 1 and seq_len + max_new <= max_ctx; VAR: embeds, lengths, stride; EXTEND: VAR's, then pos0.  The lengths stay on the device.
+enum { SLOTS = 1, SEQS = 2 };
+enum { FIXED, VAR, EXTEND };
+static int check_pass(aur_ctx* ctx, const char* who, int target, int form, int slot0, int seq0, int nseq, const void* embeds, int t, const int32_t* lens,
+                      int pos0) {
+    const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
-    const char* who = pos0 ? "aur_llm_extend_commit_var" : (lens ? "aur_llm_prefill_commit_var" : "aur_llm_prefill_commit");
-    if (!ctx->finalized || ctx->ll.empty() || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch", who);
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: slots [%d, %d) outside the batch of %d", who, slot0, slot0 + nseq, K.batch);
-    if (seq0 < 0 || seq0 + nseq > ctx->kv_seqs) return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d)", who, seq0, seq0 + nseq, ctx->kv_seqs);
-    if (seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq) return aur_fail(ctx, AUR_ERR_ARG, "%s: slot and sequence ranges overlap", who);
-    if (lens) {
-        if (int rc = var_args(ctx, who, nseq, embeds, seq_len, lens)) return rc;
-    } else if (seq_len < 1 || seq_len + K.max_new > ctx->cfg.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "seq_len %d + max_new %d exceeds max_ctx %d", seq_len, K.max_new, ctx->cfg.max_ctx);
-    hipStream_t s = (hipStream_t)stream;
+    if (!ctx->finalized || ctx->ll.empty()) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
+    if (K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "%s: no active batch (aur_begin_batch)", who);
+    if ((target & SLOTS) && (nseq < 1 || slot0 < 0 || slot0 + nseq > K.batch))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: slots [%d, %d) outside the batch of %d (aur_begin_batch)", who, slot0, slot0 + nseq, K.batch);
+    if ((target & SEQS) && (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", who, seq0, seq0 + nseq, ctx->kv_seqs);
+    if (target == (SLOTS | SEQS) && seq0 != slot0 && seq0 < slot0 + nseq && slot0 < seq0 + nseq)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: slot and sequence ranges overlap", who);
+    if (form == FIXED) {
+        if (!embeds) return aur_fail(ctx, AUR_ERR_ARG, "%s: null embeds", who);
+        if (t < 1 || t + K.max_new > g.max_ctx) return aur_fail(ctx, AUR_ERR_ARG, "%s: seq_len %d + max_new %d exceeds max_ctx %d", who, t, K.max_new, g.max_ctx);
+        return AUR_OK;
+    }
+    // sequences `t` = stride rows apart
+    if (!embeds || !lens) return aur_fail(ctx, AUR_ERR_ARG, "%s: null %s", who, !embeds ? "embeds" : "seq_lens_dev");
+    if (t < 32 || t % 32) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d is not a positive multiple of 32", who, t);
+    if (t > ctx->l_ctx_pad) return aur_fail(ctx, AUR_ERR_ARG, "%s: stride %d exceeds the %d positions of a sequence's KV pages", who, t, ctx->l_ctx_pad);
+    if (nseq > g.max_batch) return aur_fail(ctx, AUR_ERR_ARG, "%s: %d sequences exceed the front-end scratch of max_batch %d", who, nseq, g.max_batch);
+    if (form == VAR) return AUR_OK;
+    // the host checks what it can see of a pass that starts behind [0, pos0)
+    if (pos0 < g.page_tokens || pos0 % g.page_tokens)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d is not a positive multiple of the %d-token page", who, pos0, g.page_tokens);
+    if ((int64_t)pos0 + t > ctx->l_ctx_pad)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d + stride %d exceeds the %d positions of a sequence's KV pages", who, pos0, t, ctx->l_ctx_pad);
+    return AUR_OK;
+}
+
+// ---- the three tails of a pass.  BATCH: layers + first tokens of slots [slot0 ..) = the pass's sequences.  STAGE: layers only, into any
+// KV sequences (normally the spare ones): its own "prefill" timer interval, opened and closed on THIS stream.  COMMIT (decode stream,
+// possibly several stages later; timed as "prefill_commit"): slots [slot0 ..) exchange page-table rows with the staged sequences
+// [p.seq0 ..), are reset and receive their first tokens from the staged pass's last rows.
+enum { BATCH, STAGE, COMMIT };
+static int run_pass(aur_ctx* ctx, int kind, const PrefillPass& p, int slot0, hipStream_t s) {
+    if (kind != COMMIT) {
+        if (int rc = prefill_layers(ctx, p, s)) return rc;
+        if (kind == BATCH) return prefill_first_tokens(ctx, slot0, p, "prefill", s);
+        stage_end(ctx, "prefill", s);
+        return AUR_OK;
+    }
+    const aur_ctx::Bank& K = ctx->bank();
+    const int nseq = p.nseq, seq0 = p.seq0;
     stage_begin(ctx, "prefill_commit", s);
     if (seq0 != slot0) {
         const int n = nseq * ctx->l_max_pages;
@@ -1235,76 +1322,53 @@ static int prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq
     CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
     if (int rc = logprob_clear(ctx, K, slot0, nseq, s)) return rc;
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, seq_len, s, "prefill_commit", lens, pos0);
+    return prefill_first_tokens(ctx, slot0, p, "prefill_commit", s);
 }
-extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
-    return prefill_commit(ctx, slot0, nseq, seq0, embeds, seq_len, stream, nullptr);
-}
-extern "C" int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride,
-                                          const int32_t* seq_lens_dev, void* stream) {
-    if (!seq_lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_commit_var: null seq_lens_dev");
-    return prefill_commit(ctx, slot0, nseq, seq0, embeds, stride, stream, seq_lens_dev);
-}
-extern "C" int aur_llm_prefill(aur_ctx* ctx, int32_t slot, void* embeds, int32_t seq_len, void* stream) {
-    return aur_llm_prefill_batch(ctx, slot, 1, embeds, seq_len, stream);
+// an entry point = its name, its tail, its form: slots [slot0 ..) for BATCH / COMMIT, KV sequences [seq0 ..) for the rows (BATCH: seq0 == slot0)
+static int prefill_entry(aur_ctx* ctx, const char* who, int kind, int form, int slot0, int seq0, int nseq, void* embeds, int t, const int32_t* lens,
+                         int pos0, void* stream) {
+    const int target = kind == BATCH ? SLOTS : kind == STAGE ? SEQS : SLOTS | SEQS;
+    if (int rc = check_pass(ctx, who, target, form, slot0, seq0, nseq, embeds, t, lens, pos0)) return rc;
+    return run_pass(ctx, kind, PrefillPass{seq0, nseq, (half_t*)embeds, t, lens, pos0, true}, slot0, (hipStream_t)stream);
 }
 
+extern "C" int aur_llm_prefill(aur_ctx* ctx, int32_t slot, void* embeds, int32_t seq_len, void* stream) {
+    return prefill_entry(ctx, "aur_llm_prefill", BATCH, FIXED, slot, slot, 1, embeds, seq_len, nullptr, 0, stream);
+}
+extern "C" int aur_llm_prefill_batch(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t seq_len, void* stream) {
+    return prefill_entry(ctx, "aur_llm_prefill_batch", BATCH, FIXED, slot0, slot0, nseq, embeds, seq_len, nullptr, 0, stream);
+}
+extern "C" int aur_llm_prefill_stage(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t seq_len, void* stream) {
+    return prefill_entry(ctx, "aur_llm_prefill_stage", STAGE, FIXED, 0, seq0, nseq, embeds, seq_len, nullptr, 0, stream);
+}
+extern "C" int aur_llm_prefill_commit(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t seq_len, void* stream) {
+    return prefill_entry(ctx, "aur_llm_prefill_commit", COMMIT, FIXED, slot0, seq0, nseq, embeds, seq_len, nullptr, 0, stream);
+}
 extern "C" int aur_llm_prefill_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev,
                                          void* stream) {
-    const int B = ctx->bank().batch;
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
-    if (int rc = var_args(ctx, "aur_llm_prefill_batch_var", nseq, embeds, stride, seq_lens_dev)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = prefill_layers(ctx, slot0, nseq, embeds, stride, s, "aur_llm_prefill_batch_var", seq_lens_dev)) return rc;
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, stride, s, "prefill", seq_lens_dev);
+    return prefill_entry(ctx, "aur_llm_prefill_batch_var", BATCH, VAR, slot0, slot0, nseq, embeds, stride, seq_lens_dev, 0, stream);
 }
 extern "C" int aur_llm_prefill_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t stride, const int32_t* seq_lens_dev,
                                          void* stream) {
-    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
-        return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_prefill_stage_var: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", seq0, seq0 + nseq, ctx->kv_seqs);
-    if (int rc = var_args(ctx, "aur_llm_prefill_stage_var", nseq, embeds, stride, seq_lens_dev)) return rc;
-    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, (hipStream_t)stream, "aur_llm_prefill_stage_var", seq_lens_dev)) return rc;
-    stage_end(ctx, "prefill", (hipStream_t)stream);
-    return AUR_OK;
+    return prefill_entry(ctx, "aur_llm_prefill_stage_var", STAGE, VAR, 0, seq0, nseq, embeds, stride, seq_lens_dev, 0, stream);
 }
-
-// ---- prefill that starts at a position > 0: the rows of this pass are positions [pos0, pos0 + len_i) of sequences whose pages already hold
-// [0, pos0) (an earlier prefill, or aur_kv_copy_prefix from a sequence with the same leading rows).  The layer stack is the one above
-// with pos0 added to every position; the host checks what it can see, the lengths stay on the device.
-static int extend_pos_args(aur_ctx* ctx, const char* who, int pos0, int stride) {
-    if (pos0 < ctx->cfg.page_tokens || pos0 % ctx->cfg.page_tokens)
-        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d is not a positive multiple of the %d-token page", who, pos0, ctx->cfg.page_tokens);
-    if ((int64_t)pos0 + stride > ctx->l_ctx_pad)
-        return aur_fail(ctx, AUR_ERR_ARG, "%s: pos0 %d + stride %d exceeds the %d positions of a sequence's KV pages", who, pos0, stride, ctx->l_ctx_pad);
-    return AUR_OK;
+extern "C" int aur_llm_prefill_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t stride,
+                                          const int32_t* seq_lens_dev, void* stream) {
+    return prefill_entry(ctx, "aur_llm_prefill_commit_var", COMMIT, VAR, slot0, seq0, nseq, embeds, stride, seq_lens_dev, 0, stream);
 }
-static int extend_args(aur_ctx* ctx, const char* who, int nseq, const void* embeds, int pos0, int stride, const int32_t* lens) {
-    if (int rc = var_args(ctx, who, nseq, embeds, stride, lens)) return rc;
-    return extend_pos_args(ctx, who, pos0, stride);
-}
+// prefill that starts at a position > 0: the pages already hold [0, pos0) (an earlier prefill, or aur_kv_copy_prefix from a sequence with
+// the same leading rows).  The layer stack is the one above with pos0 added to every position.
 extern "C" int aur_llm_extend_batch_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride,
                                         const int32_t* new_lens_dev, void* stream) {
-    const int B = ctx->bank().batch;
-    if (nseq < 1 || slot0 < 0 || slot0 + nseq > B) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_batch_var: slots [%d, %d) outside the batch of %d (aur_begin_batch)", slot0, slot0 + nseq, B);
-    if (int rc = extend_args(ctx, "aur_llm_extend_batch_var", nseq, embeds, pos0, stride, new_lens_dev)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = prefill_layers(ctx, slot0, nseq, embeds, stride, s, "aur_llm_extend_batch_var", new_lens_dev, pos0)) return rc;
-    return prefill_first_tokens(ctx, slot0, nseq, embeds, stride, s, "prefill", new_lens_dev, pos0);
+    return prefill_entry(ctx, "aur_llm_extend_batch_var", BATCH, EXTEND, slot0, slot0, nseq, embeds, stride, new_lens_dev, pos0, stream);
 }
 extern "C" int aur_llm_extend_stage_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void* embeds, int32_t pos0, int32_t stride,
                                         const int32_t* new_lens_dev, void* stream) {
-    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
-        return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_stage_var: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", seq0, seq0 + nseq, ctx->kv_seqs);
-    if (int rc = extend_args(ctx, "aur_llm_extend_stage_var", nseq, embeds, pos0, stride, new_lens_dev)) return rc;
-    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, (hipStream_t)stream, "aur_llm_extend_stage_var", new_lens_dev, pos0)) return rc;
-    stage_end(ctx, "prefill", (hipStream_t)stream);
-    return AUR_OK;
+    return prefill_entry(ctx, "aur_llm_extend_stage_var", STAGE, EXTEND, 0, seq0, nseq, embeds, stride, new_lens_dev, pos0, stream);
 }
 extern "C" int aur_llm_extend_commit_var(aur_ctx* ctx, int32_t slot0, int32_t nseq, int32_t seq0, void* embeds, int32_t pos0, int32_t stride,
                                          const int32_t* new_lens_dev, void* stream) {
-    if (!new_lens_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_llm_extend_commit_var: null new_lens_dev");
-    if (int rc = extend_pos_args(ctx, "aur_llm_extend_commit_var", pos0, stride)) return rc;      // stride / nseq / embeds: var_args, in prefill_commit
-    return prefill_commit(ctx, slot0, nseq, seq0, embeds, stride, stream, new_lens_dev, pos0);
+    return prefill_entry(ctx, "aur_llm_extend_commit_var", COMMIT, EXTEND, slot0, seq0, nseq, embeds, stride, new_lens_dev, pos0, stream);
 }
 
 // ---- scoring given continuations: the layer stack of a _stage_var pass, then ANY of its rows through the pick path's lm_head and
@@ -1321,19 +1385,14 @@ extern "C" int aur_llm_score_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void*
                                  const int32_t* score_rows_dev, const int32_t* score_targets_dev, int32_t nscore_cap, void* scratch,
                                  int64_t scratch_bytes, float* logprob_out, int32_t* argmax_out, float* logits_out, void* stream) {
     const char* who = "aur_llm_score_var";
-    if (nseq < 1 || seq0 < 0 || seq0 + nseq > ctx->kv_seqs)
-        return aur_fail(ctx, AUR_ERR_ARG, "%s: KV sequences [%d, %d) outside [0, %d) (max_batch + spare_slots)", who, seq0, seq0 + nseq, ctx->kv_seqs);
-    if (int rc = var_args(ctx, who, nseq, embeds, stride, lens_dev)) return rc;
-    if (pos0 != 0)
-        if (int rc = extend_pos_args(ctx, who, pos0, stride)) return rc;
+    if (int rc = check_pass(ctx, who, SEQS, pos0 ? EXTEND : VAR, 0, seq0, nseq, embeds, stride, lens_dev, pos0)) return rc;
     if (!score_rows_dev || !score_targets_dev || !logprob_out || !argmax_out || nscore_cap < 1)
         return aur_fail(ctx, AUR_ERR_ARG, "%s: null entry / output array or nscore_cap %d < 1", who, nscore_cap);
     if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < aur_score_scratch_bytes(ctx))
         return aur_fail(ctx, AUR_ERR_ARG, "%s: scratch must be 256-byte aligned and hold aur_score_scratch_bytes = %lld bytes (got %lld)", who,
                         (long long)aur_score_scratch_bytes(ctx), (long long)scratch_bytes);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = prefill_layers(ctx, seq0, nseq, embeds, stride, s, who, lens_dev, pos0, false)) return rc;
-    stage_end(ctx, "prefill", s);
+    if (int rc = run_pass(ctx, STAGE, PrefillPass{seq0, nseq, (half_t*)embeds, stride, lens_dev, pos0, false}, 0, s)) return rc;
     const aur_config& g = ctx->cfg;
     const int B = g.max_batch;
     half_t* xf = (half_t*)scratch;
@@ -1345,11 +1404,7 @@ extern "C" int aur_llm_score_var(aur_ctx* ctx, int32_t seq0, int32_t nseq, void*
         const int n = nscore_cap - j0 < B ? nscore_cap - j0 : B;
         CK(launch_score_gather((const half_t*)embeds, g.llm_hidden, score_rows_dev + j0, score_targets_dev + j0, n, B, nseq, stride, lens_dev, xf,
                                ssq, tgt, s));
-        SkinnyArgs h{};       // as lm_head_and_advance sets it up, on the caller's scratch and at the engine's capacity
-        h.xf = xf; h.W = ctx->l_head_w; h.B = B; h.Npad = ctx->l_vocab_pad; h.K = g.llm_hidden; h.n_real = g.llm_vocab;
-        h.mode = SK_LOGITS; h.out32 = lg; h.b_lo = 0; h.b_hi = n; h.ssq_in = ssq; h.norm_eps = g.llm_rms_eps;
-        h.variant = ctx->skinny_variant;
-        CK(launch_skinny(h, s));
+        CK(launch_skinny(mk_lm_head(ctx, xf, ssq, lg, B, 0, n), s));       // the pick path's launch, on the caller's scratch and at the engine's capacity
         CK(launch_score_rows(lg, n, g.llm_vocab, tgt, logprob_out + j0, argmax_out + j0, s));
         if (logits_out) CK(hipMemcpyAsync(logits_out + (int64_t)j0 * g.llm_vocab, lg, (size_t)n * g.llm_vocab * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -1409,63 +1464,6 @@ extern "C" int aur_kv_copy_prefix(aur_ctx* ctx, int32_t src_seq, int32_t dst_seq
                        ctx->l_page_halves, ctx->bank().ptab, ctx->l_max_pages, src_seq, dst_seq0, ndst);
     CK(hipGetLastError());
     return AUR_OK;
-}
-
-// ---- decode-step kernel argument builders (shared by the step and by aur_microbench)
-static SkinnyArgs mk_dec_qkv(aur_ctx* ctx, int l) {
-    const aur_config& g = ctx->cfg;
-    const aur_ctx::Bank& K = ctx->bank();
-    const int d = g.llm_hidden;
-    SkinnyArgs q{};
-    q.ssq_in = K.s_ssq_mlp; q.norm_eps = g.llm_rms_eps; q.ssq_zero = K.s_ssq_attn;
-    q.xf = K.d_x; q.W = ctx->ll[l].qkv_w; q.B = K.batch; q.b_lo = 0; q.b_hi = K.batch; q.Npad = ctx->l_qkv_npad; q.K = d;
-    q.n_real = 3 * d; q.mode = SK_QKV; q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.qbuf = ctx->d_q; q.kv = llm_kv(ctx, l);
-    q.rope = ctx->l_rope; q.pos = K.s_pos; q.seq_ids = nullptr; q.variant = ctx->skinny_variant_wide;
-    q.half_grid = ctx->decode_half;
-    return q;
-}
-static DecAttnArgs mk_dec_attn(aur_ctx* ctx, int l) {
-    const aur_config& g = ctx->cfg;
-    DecAttnArgs at{};
-    at.qbuf = ctx->d_q; at.kv = llm_kv(ctx, l); at.pos = ctx->bank().s_pos; at.seq_ids = nullptr; at.B = ctx->bank().batch; at.heads = g.llm_heads;
-    at.hd = ctx->l_hd; at.nsplit = ctx->nsplit; at.pages_per_split = ctx->pps; at.scale = 1.0f / sqrtf((float)ctx->l_hd);
-    at.part_o = ctx->d_part_o; at.part_ml = ctx->d_part_ml; at.out_f = ctx->d_attn; at.out_k32 = g.llm_hidden / 32;
-    // engines whose capacity alone gives one attention workgroup per CU and still split the context (8-15 slots of 32 heads): the splits of a
-    // (sequence, head) are the waves of one workgroup and meet in LDS - bitwise the two-launch result, one launch per layer less
-    at.local_splits = (g.max_batch * g.llm_heads >= gemm256_grid_cap() /* one attention workgroup per CU */ && (ctx->nsplit == 2 || ctx->nsplit == 4) && ctx->l_hd == 128 && ctx->attn_local) ? ctx->nsplit : 0;
-    return at;
-}
-static SkinnyArgs mk_dec_o(aur_ctx* ctx, int l) {
-    const aur_ctx::Bank& K = ctx->bank();
-    const int d = ctx->cfg.llm_hidden;
-    SkinnyArgs o{};
-    o.xf = ctx->d_attn; o.W = ctx->ll[l].o_w; o.B = K.batch; o.b_lo = 0; o.b_hi = K.batch; o.Npad = ctx->l_dpad; o.K = d; o.n_real = d;
-    o.mode = SK_ROW; o.xres = K.d_x; o.ssq_out = K.s_ssq_attn;
-    o.variant = ctx->skinny_variant; o.part = (d >= ctx->row_split_min_k || ctx->cfg.max_batch > 64) ? ctx->d_part_row : nullptr;
-    o.row_cnt = ctx->fused_reduce ? ctx->d_row_cnt : nullptr; o.half_grid = ctx->decode_half;
-    return o;
-}
-static SkinnyArgs mk_dec_gateup(aur_ctx* ctx, int l) {
-    const aur_config& g = ctx->cfg;
-    const aur_ctx::Bank& K = ctx->bank();
-    const int d = g.llm_hidden;
-    SkinnyArgs gu{};
-    gu.ssq_in = K.s_ssq_attn; gu.norm_eps = g.llm_rms_eps; gu.ssq_zero = K.s_ssq_mlp;
-    gu.xf = K.d_x; gu.W = ctx->ll[l].gateup_w; gu.B = K.batch; gu.b_lo = 0; gu.b_hi = K.batch; gu.Npad = ctx->l_gu_npad; gu.K = d;
-    gu.n_real = 2 * g.llm_mlp; gu.mode = SK_SILU_MUL; gu.out_f = ctx->d_h; gu.out_k32 = g.llm_mlp / 32; gu.variant = ctx->skinny_variant_wide;
-    gu.gu_ks = g.max_batch > 64 ? 1 : 2; gu.half_grid = ctx->decode_half;
-    return gu;
-}
-static SkinnyArgs mk_dec_down(aur_ctx* ctx, int l) {
-    const aur_config& g = ctx->cfg;
-    const aur_ctx::Bank& K = ctx->bank();
-    const int d = g.llm_hidden;
-    SkinnyArgs dn{};
-    dn.xf = ctx->d_h; dn.W = ctx->ll[l].down_w; dn.B = K.batch; dn.b_lo = 0; dn.b_hi = K.batch; dn.Npad = ctx->l_dpad; dn.K = g.llm_mlp;
-    dn.n_real = d; dn.mode = SK_ROW; dn.xres = K.d_x; dn.ssq_out = K.s_ssq_mlp;
-    dn.variant = ctx->skinny_variant; dn.part = (g.llm_mlp >= ctx->row_split_min_k || g.max_batch > 64) ? ctx->d_part_row : nullptr;
-    dn.row_cnt = ctx->fused_reduce ? ctx->d_row_cnt : nullptr; dn.half_grid = ctx->decode_half;
-    return dn;
 }
 
 // ---- the attention kernels alone on caller rows (parity tests): the production fragment writer - the QKV epilogue of the layer - then the
@@ -1552,11 +1550,8 @@ extern "C" int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, i
         hipLaunchKernelGGL(rope_identity_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ident, n);
         CK(hipGetLastError());
     }
-    SkinnyArgs q{};      // as mk_dec_qkv sets it up, without the folded norm, on the caller's rows and positions
-    q.xf = xf; q.W = (const half_t*)w_packed; q.B = rows; q.b_lo = 0; q.b_hi = rows; q.Npad = npad; q.K = kx; q.n_real = 3 * d; q.mode = SK_QKV;
-    q.q_cols = d; q.k_cols = d; q.hd = ctx->l_hd; q.qbuf = ctx->d_q; q.kv = llm_kv(ctx, 0); q.rope = rope ? ctx->l_rope : ident; q.pos = pos_dev;
-    q.seq_ids = nullptr; q.variant = ctx->skinny_variant_wide; q.half_grid = ctx->decode_half;
-    CK(launch_skinny(q, s));
+    // mk_dec_qkv's launch without the folded norm, on the caller's rows and positions
+    CK(launch_skinny(mk_sk_qkv(ctx, 0, xf, (const half_t*)w_packed, rows, kx, rope ? ctx->l_rope : ident, pos_dev, nullptr, nullptr), s));
     DecAttnArgs at = mk_dec_attn(ctx, 0);
     at.pos = pos_dev; at.B = rows;
     CK(launch_decode_attention(at, s));
@@ -1566,8 +1561,8 @@ extern "C" int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, i
 }
 
 // One decode projection alone on caller rows (parity tests): the production producer of x fragments (and sum(x^2)) at batch rows
-// [b0, b0 + rows), then launch_skinny in the structure the decode step would pick for this engine - variant, split-K partials, fused
-// reduce, k phases of gate/up, half grid exactly as mk_dec_o / mk_dec_down / mk_dec_gateup / the lm_head set them.  Everything else is
+// [b0, b0 + rows), then launch_skinny with arguments from the builders the decode step itself uses (mk_sk_row / mk_sk_gateup / mk_lm_head):
+// the structure - variant, split-K partials, fused reduce, k phases of gate/up, half grid - is mk_skinny's, stated nowhere else.  Everything else is
 // copies between the caller's row-major buffers and the fragment forms.  Scratch (the caller's): x fragments of round_up(max_batch, 16)
 // rows | residual / SiLU*up fragments | split-K partials | arrival counters.
 static int64_t proj_rows_pad(const aur_ctx* c) { return rup(c->cfg.max_batch, 16); }
@@ -1617,22 +1612,22 @@ extern "C" int aur_decode_proj_rows(aur_ctx* ctx, int32_t mode, const void* x, i
     } else if (b0 == 0) CK(launch_xfrag_pack((const half_t*)x, k, rows, k, xf, s));
     else CK(launch_xfrag_norm((const half_t*)x, k, nullptr, eps, rows, k, b0, xf, nullptr, s));  // the same rows at an offset: a plain copy
     // 2. projection
-    SkinnyArgs a{};
-    a.xf = xf; a.W = (const half_t*)w_packed; a.B = b0 + rows; a.b_lo = b0; a.b_hi = b0 + rows; a.Npad = npad; a.K = k; a.n_real = n;
-    a.mode = mode == AUR_PROJ_ROW ? SK_ROW : mode == AUR_PROJ_SILU_MUL ? SK_SILU_MUL : SK_LOGITS;
-    if (fold) { a.ssq_in = ssq_in; a.norm_eps = eps; a.ssq_zero = ssq_zero; }
-    if (a.mode == SK_ROW) {
+    const half_t* W = (const half_t*)w_packed;
+    const int B = b0 + rows;
+    if (!fold) ssq_in = ssq_zero = nullptr;
+    SkinnyArgs a;
+    if (mode == AUR_PROJ_ROW) {
         CK(launch_xfrag_pack((const half_t*)out, n, (int)rp, n, frag, s));
         CK(hipMemsetAsync(cnt, 0, (size_t)(npad / 16) * 4, s));
-        a.xres = frag; a.ssq_out = ssq_out; a.variant = ctx->skinny_variant;
-        a.part = (k >= ctx->row_split_min_k || g.max_batch > 64) ? part : nullptr;
-        a.row_cnt = ctx->fused_reduce ? cnt : nullptr; a.half_grid = ctx->decode_half;
-    } else if (a.mode == SK_SILU_MUL) {
+        a = mk_sk_row(ctx, xf, W, frag, ssq_out, part, cnt, B, b0, B, k, npad, n);
+    } else if (mode == AUR_PROJ_SILU_MUL) {
         CK(launch_xfrag_pack((const half_t*)out, n / 2, (int)rp, n / 2, frag, s));
-        a.out_f = frag; a.out_k32 = n / 64; a.variant = ctx->skinny_variant_wide; a.gu_ks = g.max_batch > 64 ? 1 : 2; a.half_grid = ctx->decode_half;
-    } else {
-        a.out32 = (float*)out; a.variant = ctx->skinny_variant;
+        a = mk_sk_gateup(ctx, xf, W, frag, B, b0, B, k, npad, n, ssq_in, ssq_zero);
+    } else {      // the production lm_head launch on the caller's weight and dimensions (and, unlike it, with an accumulator to clear)
+        a = mk_lm_head(ctx, xf, ssq_in, (float*)out, B, b0, B);
+        a.W = W; a.Npad = npad; a.K = k; a.n_real = n; a.ssq_zero = ssq_zero;
     }
+    if (fold) a.norm_eps = eps;
     CK(launch_skinny(a, s));
     // 3. results back in the caller's row-major form, all round_up(max_batch, 16) batch rows
     if (a.mode != SK_LOGITS) {
@@ -2081,13 +2076,8 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
         else if (!strcmp(kernel, "dec_o")) { CK(launch_skinny(mk_dec_o(ctx, l), s)); }
         else if (!strcmp(kernel, "dec_gateup")) { CK(launch_skinny(mk_dec_gateup(ctx, l), s)); }
         else if (!strcmp(kernel, "dec_down")) { CK(launch_skinny(mk_dec_down(ctx, l), s)); }
-        else if (!strcmp(kernel, "dec_lm_head")) {
-            SkinnyArgs h{};
-            h.ssq_in = K.s_ssq_mlp; h.norm_eps = g.llm_rms_eps;
-            h.xf = K.d_x; h.W = ctx->l_head_w; h.B = K.batch; h.b_lo = 0; h.b_hi = K.batch; h.Npad = ctx->l_vocab_pad; h.K = d;
-            h.n_real = g.llm_vocab; h.mode = SK_LOGITS; h.out32 = K.d_logits; h.variant = ctx->skinny_variant;
-            CK(launch_skinny(h, s));
-        } else if (!strcmp(kernel, "dec_pick")) {              // the token pick alone, on the logits of the last step: whichever kernel the "sampling" mode selects
+        else if (!strcmp(kernel, "dec_lm_head")) { CK(launch_skinny(mk_lm_head(ctx, K.d_x, K.s_ssq_mlp, K.d_logits, K.batch, 0, K.batch), s)); }
+        else if (!strcmp(kernel, "dec_pick")) {              // the token pick alone, on the logits of the last step: whichever kernel the "sampling" mode selects
             if (ctx->sampling)
                 CK(launch_sample_advance(K.d_logits, 0, K.batch, g.llm_vocab, K.s_samp, ctx->l_embed, d, K.eos, K.max_new, K.s_ids, K.s_len, K.s_fin,
                                          K.s_pos, K.d_x, K.s_ssq_mlp, 1, -1, s, nullptr, 0, ctx->sample_stage));
@@ -2103,7 +2093,7 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
                       : !strcmp(kernel, "pre_gateup") ? 32 : !strcmp(kernel, "pre_down") ? 64 : 0;
             if (!bit) return aur_fail(ctx, AUR_ERR_ARG, "unknown kernel '%s'", kernel);
             // scratch residual stream: l_p1 (projector scratch) is free after the splice
-            return prefill_layer(ctx, l, bit, 0, ctx->mb_nseq, ctx->l_p1, ctx->last_prefill_len, s);
+            return prefill_layer(ctx, l, bit, PrefillPass{0, ctx->mb_nseq, ctx->l_p1, ctx->last_prefill_len, nullptr, 0, true}, s);
         }
         return AUR_OK;
     };

@@ -681,39 +681,30 @@ class AuroraCapEngine:
         self._tmp = getattr(self, "_tmp", [])[-64:] + [t]         # keep alive until consumed
         return t
 
+    def _pass(self, kind: str, ids: Sequence[int], embeds: torch.Tensor, t: int, lens, pos0: Optional[int] = None):
+        """One prefill pass through the entry point that (kind, has lengths, has pos0) selects.  kind: "batch" / "stage" / "commit"; ids:
+        the leading (slot0 or seq0, nseq[, seq0]) arguments; t: the sequence length or, with lengths, the stride; pos0: the extend forms."""
+        name = f"aur_llm_{'prefill' if pos0 is None else 'extend'}_{kind}" + ("" if lens is None else "_var")
+        args = [*ids, embeds.data_ptr(), *([] if pos0 is None else [pos0]), t]
+        if lens is not None:
+            args.append(self._lens_arg(lens, ids[1], t, pos0 or 0).data_ptr())
+        check(self.ctx, getattr(self.L, name)(self.ctx, *args, self._stream()), name)
+
     def prefill_batch(self, slot0: int, nseq: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
         """embeds [nseq * round_up(seq_len, 32), d]: equal-length sequences prefetched in ONE pass (large-M GEMMs).
         seq_lens (a list, or an int32 device tensor): sequences of DIFFERENT lengths, `seq_len` rows apart (a multiple of 32);
         every sequence gets bitwise what it gets alone."""
-        if seq_lens is not None:
-            lens = self._lens_arg(seq_lens, nseq, seq_len)
-            check(self.ctx, self.L.aur_llm_prefill_batch_var(self.ctx, slot0, nseq, embeds.data_ptr(), seq_len, lens.data_ptr(), self._stream()),
-                  "aur_llm_prefill_batch_var")
-            return
-        check(self.ctx, self.L.aur_llm_prefill_batch(self.ctx, slot0, nseq, embeds.data_ptr(), seq_len, self._stream()),
-              "aur_llm_prefill_batch")
+        self._pass("batch", (slot0, nseq), embeds, seq_len, seq_lens)
 
     def prefill_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
         """The layer stack of `prefill_batch` into KV sequences [seq0, seq0 + nseq) (normally the spare ones,
         `max_batch ..`): touches no decode state, so it may run on another stream while `decode` runs."""
-        if seq_lens is not None:
-            lens = self._lens_arg(seq_lens, nseq, seq_len)
-            check(self.ctx, self.L.aur_llm_prefill_stage_var(self.ctx, seq0, nseq, embeds.data_ptr(), seq_len, lens.data_ptr(), self._stream()),
-                  "aur_llm_prefill_stage_var")
-            return
-        check(self.ctx, self.L.aur_llm_prefill_stage(self.ctx, seq0, nseq, embeds.data_ptr(), seq_len, self._stream()),
-              "aur_llm_prefill_stage")
+        self._pass("stage", (seq0, nseq), embeds, seq_len, seq_lens)
 
     def prefill_commit(self, slot0: int, nseq: int, seq0: int, embeds: torch.Tensor, seq_len: int, seq_lens=None):
         """On the decode stream, after `prefill_stage` has completed: slots [slot0 ..) take over the pages of sequences
         [seq0 ..) (which get the slots' old pages), are reset, and receive their first tokens."""
-        if seq_lens is not None:
-            lens = self._lens_arg(seq_lens, nseq, seq_len)
-            check(self.ctx, self.L.aur_llm_prefill_commit_var(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), seq_len, lens.data_ptr(),
-                                                              self._stream()), "aur_llm_prefill_commit_var")
-            return
-        check(self.ctx, self.L.aur_llm_prefill_commit(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), seq_len, self._stream()),
-              "aur_llm_prefill_commit")
+        self._pass("commit", (slot0, nseq, seq0), embeds, seq_len, seq_lens)
 
     # ------------------------------------------------------------------ shared prefixes
     def kv_copy_prefix(self, src_seq: int, dst_seq0: int, ndst: int, tokens: int):
@@ -725,21 +716,15 @@ class AuroraCapEngine:
         """`prefill_batch(seq_lens=)` for slots that already hold positions [0, pos0) (`kv_copy_prefix`, or an earlier prefill): embeds
         [nseq * stride, d], rows [i * stride, i * stride + new_lens[i]) = positions [pos0, pos0 + new_lens[i]).  Bitwise what
         `prefill(slot, full_embeds, pos0 + new_lens[i])` gives.  new_lens: a list (checked here) or an int32 device tensor."""
-        lens = self._lens_arg(new_lens, nseq, stride, pos0)
-        check(self.ctx, self.L.aur_llm_extend_batch_var(self.ctx, slot0, nseq, embeds.data_ptr(), pos0, stride, lens.data_ptr(), self._stream()),
-              "aur_llm_extend_batch_var")
+        self._pass("batch", (slot0, nseq), embeds, stride, new_lens, pos0)
 
     def extend_stage(self, seq0: int, nseq: int, embeds: torch.Tensor, pos0: int, stride: int, new_lens):
         """The layer stack of `extend_batch` into KV sequences [seq0, seq0 + nseq): touches no decode state (see `prefill_stage`)."""
-        lens = self._lens_arg(new_lens, nseq, stride, pos0)
-        check(self.ctx, self.L.aur_llm_extend_stage_var(self.ctx, seq0, nseq, embeds.data_ptr(), pos0, stride, lens.data_ptr(), self._stream()),
-              "aur_llm_extend_stage_var")
+        self._pass("stage", (seq0, nseq), embeds, stride, new_lens, pos0)
 
     def extend_commit(self, slot0: int, nseq: int, seq0: int, embeds: torch.Tensor, pos0: int, stride: int, new_lens):
         """`prefill_commit` for sequences staged by `extend_stage` (same pos0, stride and lengths): decode position pos0 + new_lens[i]."""
-        lens = self._lens_arg(new_lens, nseq, stride, pos0)
-        check(self.ctx, self.L.aur_llm_extend_commit_var(self.ctx, slot0, nseq, seq0, embeds.data_ptr(), pos0, stride, lens.data_ptr(),
-                                                         self._stream()), "aur_llm_extend_commit_var")
+        self._pass("commit", (slot0, nseq, seq0), embeds, stride, new_lens, pos0)
 
     def _extend_rows(self, vis: torch.Tensor, plan: dict, fork: int, out: torch.Tensor):
         """Rows [fork, seq_len) of a sibling prompt's spliced embeddings -> out[: seq_len - fork] (its own plan over the kept visual

@@ -342,7 +342,8 @@ int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, 
                          int32_t rope, void* scratch, int64_t scratch_bytes, void* out, void* stream);
 
 /* One decode projection alone on caller rows (tests/test_gpu_skinny_modes.py): the producer of x fragments, then launch_skinny in the
- * structure the decode step of THIS engine picks (capacity, "skinny_row_split_min_k", "decode_fused_reduce", "decode_half_grid").
+ * structure the decode step of THIS engine picks (capacity, "skinny_row_split_min_k", "decode_fused_reduce", "decode_half_grid"): the
+ * arguments come from the builders the step itself calls, and the rule is stated once, in mk_skinny (aurora_amd/csrc/engine.hip).
  * x fp16 [rows, k] lands at batch rows [b0, b0 + rows) (b0 + rows <= max_batch; k % 128 == 0); every other batch row of the x fragments,
  * up to rp = round_up(max_batch, 16), holds `fill`.  fold = 1: the producer is the prefill hand-over's (x fragments + sum(x^2) into
  * ssq_in), the projection scales by rsqrt(sum / k + eps) and must clear ssq_zero, which the entry fills with a non-zero pattern first;
@@ -458,7 +459,7 @@ int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int3
  * dec_attn_local, decode_fused_reduce and decode_half_grid are bit-neutral; dec_attn_pps / skinny_row_split_min_k change how fp32
  * partial sums are partitioned (same tolerance, not bit-comparable across settings).  Knobs whose losing arm was measured twice are
  * gone (rounds 5-6): the decode structure is a function of the engine's capacity alone (x fragments per wave up to 32 slots, x through
- * LDS above), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
+ * LDS above; mk_skinny in aurora_amd/csrc/engine.hip is the one place that picks it, for the step, aur_microbench and the parity entries), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
 int aur_set_option(aur_ctx* ctx, const char* name, int64_t value);
 /* Time one kernel of the LLM path in isolation on the current generation state (after aur_llm_prefill):
  * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), pre_norm, pre_qkv, pre_attn,

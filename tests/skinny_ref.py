@@ -65,7 +65,9 @@ Structure = namedtuple("Structure", "kind NW KS KC NBUF S")
 
 
 def structure(mode, max_batch, K, nb, row_split_min_k=8192, half=False):
-    """the structure launch_skinny picks (decode.hip launch_skinny_nb / launch_skx_nb) for an engine of `max_batch` slots, nb column groups"""
+    """the structure launch_skinny picks (decode.hip launch_skinny_nb / launch_skx_nb) for an engine of `max_batch` slots, nb column groups.
+    The library states the rule once, in mk_skinny (aurora_amd/csrc/engine.hip), for the decode step and the parity entries alike; this is
+    the tests' independent statement of it."""
     variant = 1 if max_batch > 32 else 0
     if mode == "silu_mul":                      # the wide projections go through LDS at every capacity
         if max_batch > 64:                      # gu_ks == 1

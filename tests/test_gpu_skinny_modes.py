@@ -222,6 +222,29 @@ def test_new_entry_equals_linear_skinny(cap):
         assert torch.equal(got[: rows * N].view(rows, N), eng.linear_skinny(c["x"], c["w"]).cpu()), (rows, K, N)
 
 
+@pytest.mark.parametrize("cap", [2, 64])
+def test_logits_entry_takes_the_production_lm_head_route(cap):
+    """The first-token logits of a 40-row prefill are, bit for bit, the "logits" mode with the folded norm applied to row 39 of the embeds
+    buffer - the final hidden state the prefill left there - on an engine of 2 slots (x per wave) and of 64 (x through LDS): the entry
+    and the pick path issue one launch, built in one place.  The engine keeps its packed head only as an anonymous device tensor, so the
+    weight is packed again here exactly as AuroraCapEngine._load_llm does: lm_head.weight times the final norm's weight in fp32, fp16."""
+    from tests.test_gpu_llm import LLM_CFGS, make_engine, padded
+    cfg, L = LLM_CFGS["hd32"], 40
+    d, V = cfg["hidden_size"], cfg["vocab_size"]
+    eng, w = make_engine(cfg, 21, max_batch=cap)
+    try:
+        emb = padded(torch.randn(L, d, generator=torch.Generator().manual_seed(22)).half().float())
+        eng.begin_batch(1, 4, None)
+        eng.prefill(0, emb, L)
+        want = eng.logits()[0].cpu()
+        head = (w["lm_head.weight"].detach().to("cuda", torch.float32) * w["norm.weight"].detach().to("cuda", torch.float32)[None, :]).half()
+        init = torch.full((R.rup(cap, 16) * V + GUARD,), SENTINEL, dtype=torch.float32)
+        got = eng.decode_proj_rows("logits", emb[L - 1:L], eng.pack(head, R.rup(V, 256), d), V, init, fold=True, eps=cfg["rms_norm_eps"])["out"].cpu()
+        assert torch.equal(got[:V].view(torch.int32), want.view(torch.int32))
+    finally:
+        eng.close()
+
+
 def test_decode_proj_rows_rejects_bad_arguments():
     from aurora_amd._lib import AuroraHipError
     eng = engine(64)
