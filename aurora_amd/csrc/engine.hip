@@ -86,6 +86,11 @@ struct aur_ctx {
     int tome_fused_ln = 1;                                                      // 1: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge launch (bitwise norm_kernel's result; 0 = its own launch, A/B and test only)
     int sampling = 0, sample_stage = 1;                                         // the token pick: 0 argmax_advance_kernel, 1 sample_advance_kernel (row staged in LDS / re-read from L2)
     int logit_rules = 0;                                                        // 1: logit_rules_apply_kernel ahead of every pick, logit_rules_restore_kernel behind it (the slots' aur_logit_rules records)
+    int stop_rules = 0;                                                         // 1: stop_check_kernel behind every pick (the slots' aur_stop_rules records)
+    const int32_t* stop_off = nullptr;                                          // aur_stop_vocab: the caller's token byte table (device memory)
+    const uint8_t* stop_bytes = nullptr;
+    int stop_vocab = 0;
+    int64_t stop_nbytes = 0;
     int fused_reduce = 0;                                                       // 1: the split-K reduce runs inside the projection kernel
     // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graphs) so
     // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  Every generation call
@@ -99,6 +104,7 @@ struct aur_ctx {
         aur_logit_rules* s_rules;                            // per-slot logit rules (aur_slot_logit_rules); all zero = neutral
         int32_t* lr_cnt;                                     // entries of each slot's side list written by the last apply
         void* lr_save = nullptr;                             // side lists [max_batch][max_new_tokens + 1] of (index, original logit): allocated by option "logit_rules" 1
+        aur_stop_rules* s_stop = nullptr;                    // per-slot stop records (aur_slot_stop) [max_batch]; all zero = neutral: allocated by option "stop_rules" 1
         int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
         // log-probabilities of generated tokens (aur_logprob_enable): the caller's buffer, nullptr = off.  lp_len [max_batch]: tokens of
         // slot b recorded so far; lp [b][max_new], lp_top_id / lp_top_lp [b][max_new][lp_top_n]: rows max_new apart, like s_ids
@@ -365,6 +371,7 @@ extern "C" void aur_destroy(aur_ctx* ctx) {
     for (auto& K : ctx->banks) {
         drop_graphs(K);
         if (K.lr_save) (void)hipFree(K.lr_save);
+        if (K.s_stop) (void)hipFree(K.s_stop);
     }
     for (auto& ug : ctx->ugraphs)
         if (ug.exec) (void)hipGraphExecDestroy(ug.exec);
@@ -1061,6 +1068,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.s_pos, 0, (size_t)g.max_batch * 4, s));
     CK(hipMemsetAsync(K.s_samp, 0, (size_t)g.max_batch * sizeof(aur_sampling), s));      // every slot greedy until aur_slot_sampling says otherwise
     CK(hipMemsetAsync(K.s_rules, 0, (size_t)g.max_batch * sizeof(aur_logit_rules), s));  // every slot neutral until aur_slot_logit_rules says otherwise
+    if (K.s_stop) CK(hipMemsetAsync(K.s_stop, 0, (size_t)g.max_batch * sizeof(aur_stop_rules), s));   // every slot without a stop request until aur_slot_stop says otherwise
     CK(hipMemsetAsync(K.s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
     const size_t bp = (size_t)rup(g.max_batch, 16);       // unused fragment lanes must hold finite values
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
@@ -1090,6 +1098,10 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     if (K.lp_len)
         CK(launch_token_logprob(K.d_logits, b0, nb, g.llm_vocab, K.s_ids, K.s_len, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id,
                                 K.lp_top_lp, s));
+    // stop ids / stop strings / budget on the token just appended: sets `finished` of a slot that stops, as the pick does for an EOS
+    if (ctx->stop_rules)
+        CK(launch_stop_check(b0, nb, K.s_stop, K.s_ids, K.max_new, K.s_len, K.max_new, K.s_fin, ctx->stop_off, ctx->stop_bytes, ctx->stop_vocab,
+                             ctx->stop_nbytes, s));
     return AUR_OK;
 }
 
@@ -1843,6 +1855,7 @@ extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     CK(hipMemsetAsync(K.s_pos + slot, 0, 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
     CK(hipMemsetAsync(K.s_rules + slot, 0, sizeof(aur_logit_rules), s));
+    if (K.s_stop) CK(hipMemsetAsync(K.s_stop + slot, 0, sizeof(aur_stop_rules), s));
     return logprob_clear(ctx, K, slot, 1, s);
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
@@ -1984,6 +1997,41 @@ extern "C" int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, i
     CK(e);
     return AUR_OK;
 }
+extern "C" int aur_slot_stop(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_stop_rules* rules_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_stop")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.s_stop) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_stop: needs option \"stop_rules\" 1 (it allocates the records)");
+    if (nslots < 1 || slot0 + nslots > K.batch || !rules_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_stop: slots [%d, %d) outside the batch of %d, or null rules", slot0, slot0 + nslots, K.batch);
+    CK(hipMemcpyAsync(K.s_stop + slot0, rules_dev, (size_t)nslots * sizeof(aur_stop_rules), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AUR_OK;
+}
+static bool stop_table_ok(const int32_t* off, const uint8_t* bytes, int32_t vocab, int64_t nbytes) {
+    if (!off && !bytes && vocab == 0 && nbytes == 0) return true;                      // no table: no string matches
+    return off && bytes && vocab >= 1 && nbytes >= 1 && nbytes <= 0x7fffffff && !((uintptr_t)off & 3);
+}
+extern "C" int aur_stop_vocab(aur_ctx* ctx, const int32_t* offsets_dev, const uint8_t* bytes_dev, int32_t vocab, int64_t nbytes) {
+    NO_CAPTURE("aur_stop_vocab");
+    if (!stop_table_ok(offsets_dev, bytes_dev, vocab, nbytes))
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_stop_vocab: offsets [vocab + 1] and bytes [nbytes] with vocab >= 1 and 1 <= nbytes < 2^31, or all of them 0");
+    // the pointers are by-value kernel arguments frozen inside the captured decode graphs of every bank
+    if (ctx->stop_rules) {
+        if (ctx->banks[0].graph || ctx->banks[0].graph_h || ctx->banks[1].graph || ctx->banks[1].graph_h) (void)hipDeviceSynchronize();
+        for (auto& K : ctx->banks) drop_graphs(K);
+    }
+    ctx->stop_off = offsets_dev; ctx->stop_bytes = bytes_dev; ctx->stop_vocab = vocab; ctx->stop_nbytes = nbytes;
+    return AUR_OK;
+}
+extern "C" int aur_stop_rows(aur_ctx* ctx, int32_t rows, const int32_t* ids_dev, int32_t ids_stride, const int32_t* lens_dev,
+                             const aur_stop_rules* rules_dev, int32_t* finished_dev, int32_t batch_max_new, const int32_t* offsets_dev,
+                             const uint8_t* bytes_dev, int32_t vocab, int64_t nbytes, void* stream) {
+    if (!ctx || !ids_dev || !lens_dev || !rules_dev || !finished_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_stop_rows: null argument");
+    if (rows < 1 || ids_stride < 1 || ((uintptr_t)rules_dev & 7))
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_stop_rows: rows %d < 1, ids_stride %d < 1 or records not 8-byte aligned", rows, ids_stride);
+    if (!stop_table_ok(offsets_dev, bytes_dev, vocab, nbytes)) return aur_fail(ctx, AUR_ERR_ARG, "aur_stop_rows: byte table (see aur_stop_vocab)");
+    CK(launch_stop_check(0, rows, rules_dev, ids_dev, ids_stride, lens_dev, batch_max_new, finished_dev, offsets_dev, bytes_dev, vocab, nbytes,
+                         (hipStream_t)stream));
+    return AUR_OK;
+}
 extern "C" int aur_copy_logits(aur_ctx* ctx, float* dst_dev, void* stream) {
     const aur_ctx::Bank& K = ctx->bank();
     if (K.batch < 1 || !dst_dev) return aur_fail(ctx, AUR_ERR_STATE, "aur_copy_logits: no active batch");
@@ -2042,6 +2090,17 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
                 if (!ctx->banks[bk].lr_save)
                     CK(hipMalloc(&ctx->banks[bk].lr_save, (size_t)logit_rules_save_bytes(ctx->cfg.max_batch, ctx->cfg.max_new_tokens)));
         ctx->logit_rules = (int)value;
+    } else if (!strcmp(name, "stop_rules")) {
+        // whether stop_check_kernel follows the pick is frozen inside the captured decode graphs, like "sampling": they are re-captured.
+        // The records are allocated here, once, outside any capture, neutral; they live as long as the ctx
+        if (value < 0 || value > 1) return aur_fail(ctx, AUR_ERR_ARG, "%s must be 0 or 1", name);
+        if (value)
+            for (int bk = 0; bk < 2; ++bk)
+                if (!ctx->banks[bk].s_stop) {
+                    CK(hipMalloc((void**)&ctx->banks[bk].s_stop, (size_t)ctx->cfg.max_batch * sizeof(aur_stop_rules)));
+                    CK(hipMemset(ctx->banks[bk].s_stop, 0, (size_t)ctx->cfg.max_batch * sizeof(aur_stop_rules)));
+                }
+        ctx->stop_rules = (int)value;
     } else if (!strcmp(name, "decode_half_grid")) {
         // the following aur_llm_decode calls go to a stream that owns half of the CUs: QKV / gate-up launch half as many workgroups
         // with twice the tiles (decode.hip launch_skx_nb); bitwise the same tokens.  Keeps both captured graphs.
@@ -2088,6 +2147,10 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
             if (!ctx->logit_rules) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_rules needs option \"logit_rules\" 1");
             CK(launch_logit_rules_apply(K.d_logits, 0, K.batch, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
             CK(launch_logit_rules_restore(K.d_logits, 0, K.batch, g.llm_vocab, K.max_new, K.lr_save, K.lr_cnt, s));
+        } else if (!strcmp(kernel, "dec_stop")) {              // the stop check alone, on the history and the records of the last step
+            if (!ctx->stop_rules) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_stop needs option \"stop_rules\" 1");
+            CK(launch_stop_check(0, K.batch, K.s_stop, K.s_ids, K.max_new, K.s_len, K.max_new, K.s_fin, ctx->stop_off, ctx->stop_bytes,
+                                 ctx->stop_vocab, ctx->stop_nbytes, s));
         } else {
             int bit = !strcmp(kernel, "pre_norm") ? 1 : !strcmp(kernel, "pre_qkv") ? 2 : !strcmp(kernel, "pre_attn") ? 4 : !strcmp(kernel, "pre_o") ? 8
                       : !strcmp(kernel, "pre_gateup") ? 32 : !strcmp(kernel, "pre_down") ? 64 : 0;

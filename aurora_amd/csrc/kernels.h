@@ -226,6 +226,14 @@ hipError_t launch_logit_rules_apply(float* logits, int b0, int nb, int vocab, co
 hipError_t launch_logit_rules_restore(float* logits, int b0, int nb, int vocab, int ids_stride, const void* save, const int32_t* save_cnt,
                                       hipStream_t s);
 
+// ---- stop.hip: stop ids / stop strings / per-request budget behind the pick, on slots [b0, b0 + nb): sets finished[b] of an unfinished
+// slot whose newest token stops it, nothing else.  ids [.., ids_stride] / lens: the slots' generated tokens; offsets int32 [vocab + 1] /
+// bytes uint8 [nbytes]: the bytes every token decodes to (nullptr: no string matches)
+struct aur_stop_rules;
+hipError_t launch_stop_check(int b0, int nb, const aur_stop_rules* rules, const int32_t* ids, int ids_stride, const int32_t* lens,
+                             int batch_max_new, int32_t* finished, const int32_t* offsets, const uint8_t* bytes, int vocab, int64_t nbytes,
+                             hipStream_t s);
+
 // ---- score.hip: log-probability of a target token under a logits row (+ the row's first argmax), and the row-list gather that feeds
 // any rows of a prefill pass to the pick path's lm_head (aur_llm_score_var)
 hipError_t launch_score_rows(const float* logits, int rows, int vocab, const int32_t* targets, float* logprob_out, int32_t* argmax_out,

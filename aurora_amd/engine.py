@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from . import logit_rules as LR
+from . import stopping as ST
 from . import sampling as S
 from .scoring import check_logprobs
 from ._lib import AurConfig, check
@@ -338,6 +339,10 @@ class AuroraCapEngine:
         self._samp_stage = None                          # device staging of aur_sampling records, one row per (bank, slot)
         self._rules_mode = False                         # ctx option "logit_rules": flipped by the first request with non-neutral rules, sticky
         self._rules_stage = None                         # device staging of aur_logit_rules records, one row per (bank, slot)
+        self._stop_mode = False                          # ctx option "stop_rules": flipped by the first request with a non-neutral stop record, sticky
+        self._stop_stage = None                          # device staging of aur_stop_rules records, one row per (bank, slot)
+        self._stop_table = None                          # set_stop_vocab: the tokenizer's byte table on the host (validation, finish_reason) ...
+        self._stop_table_dev = None                      # ... and on the device (caller-owned memory of aur_stop_vocab)
         self._lp_bufs: Dict[int, torch.Tensor] = {}      # bank -> the caller-owned state of aur_logprob_enable (kept once allocated)
         self._lp_top: Dict[int, int] = {}                # bank -> top_n it records with; absent = off
         self.c = c
@@ -1046,6 +1051,90 @@ class AuroraCapEngine:
         if rules is not None:
             self.slot_logit_rules(0, LR.records(rules, B))
 
+    # ------------------------------------------------------------------ stop conditions
+    def set_stop_vocab(self, table):
+        """Hand the ctx the bytes every vocabulary entry decodes to: `stopping.token_bytes(tokenizer)`, built once per tokenizer -
+        (offsets int32 [V + 1], bytes uint8).  Needed before any request with stop strings; None takes it back.  Decode graphs that
+        froze the previous table are re-captured."""
+        if table is None:
+            check(self.ctx, self.L.aur_stop_vocab(self.ctx, None, None, 0, 0), "aur_stop_vocab")
+            self._stop_table = self._stop_table_dev = None
+            return
+        off = np.ascontiguousarray(table[0], np.int32)
+        data = np.ascontiguousarray(table[1], np.uint8)
+        if off.ndim != 1 or len(off) < 2 or data.ndim != 1 or len(data) < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] > len(data):
+            raise ValueError("stop vocabulary: offsets int32 [V + 1], ascending from 0, into bytes uint8")
+        if int(np.diff(off).max()) > ST.MAX_TOKEN_BYTES:
+            raise ValueError(f"stop vocabulary: a token of more than {ST.MAX_TOKEN_BYTES} bytes")
+        dev = (torch.from_numpy(off).to(self.dev), torch.from_numpy(data).to(self.dev))
+        torch.cuda.synchronize()
+        check(self.ctx, self.L.aur_stop_vocab(self.ctx, dev[0].data_ptr(), dev[1].data_ptr(), len(off) - 1, len(data)), "aur_stop_vocab")
+        self._stop_table, self._stop_table_dev = (off, data), dev
+
+    def _stop_on(self):
+        """The first request with a non-neutral stop record puts stop_check_kernel behind the ctx's token pick (decode graphs are
+        re-captured once, the banks' records are allocated); slots whose record is neutral stop on the EOS and the batch's limit
+        alone, as before.  Sticky, like `_sampling_on`.  A process that never asks never gets here."""
+        if not self._stop_mode:
+            self._drop_front_graphs()
+            self.set_option("stop_rules", 1)
+            self._stop_mode = True
+
+    def _stop_records(self, stop, count: int, max_new_tokens: int):
+        """A call's `stop=` for `count` sequences -> validated records, or None (then the call is one without the argument)."""
+        return ST.per_sequence(stop, count, max_new_tokens, self._stop_table)
+
+    def slot_stop(self, slot0: int, recs: np.ndarray):
+        """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_stop_rules records (`stopping.records`): staged in
+        device memory and copied into the bank when the stream gets there - before the prefill / commit that picks the first token."""
+        recs = np.ascontiguousarray(recs, dtype=ST.RECORD)
+        n = len(recs)
+        if n < 1 or slot0 < 0 or slot0 + n > self.max_batch:
+            raise ValueError(f"slots [{slot0}, {slot0 + n}) outside an engine of {self.max_batch} slots")
+        if self._stop_stage is None:
+            self._stop_stage = torch.zeros(2 * self.max_batch, ST.RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        row0 = self._bank * self.max_batch + slot0
+        dst = self._stop_stage[row0: row0 + n]
+        dst.copy_(torch.from_numpy(recs.view(np.uint8).reshape(n, ST.RECORD.itemsize).copy()))     # torch's current stream: _stream() orders ours behind it
+        check(self.ctx, self.L.aur_slot_stop(self.ctx, slot0, n, dst.data_ptr(), self._stream()), "aur_slot_stop")
+
+    def _begin_stop(self, stops, B: int):
+        """After begin_batch (which makes every slot neutral): the records of slots [0, B) for a call with stop records."""
+        if stops is not None:
+            self.slot_stop(0, ST.records(stops))
+
+    def stop_rows(self, histories: Sequence[Sequence[int]], recs: np.ndarray, batch_max_new: int, finished=None, table=None,
+                  ids_stride: Optional[int] = None) -> np.ndarray:
+        """stop_check_kernel alone (aur_stop_rows): one generated history and one aur_stop_rules record per row -> the rows'
+        `finished` flags (numpy int32) behind the kernel.  finished: the flags before it (default: none set); a row whose flag is
+        set is skipped.  table: (offsets, bytes) as `stopping.token_bytes` gives it, or None (no string matches).  ids_stride: the
+        row stride of the history buffer (default: the longest history, at least 1)."""
+        rows = len(histories)
+        recs = np.ascontiguousarray(recs, dtype=ST.RECORD)
+        assert rows >= 1 and len(recs) == rows
+        stride = max([1] + [len(h) for h in histories]) if ids_stride is None else int(ids_stride)
+        assert stride >= 1 and all(len(h) <= stride for h in histories)
+        ids = np.zeros((rows, stride), np.int32)
+        for i, h in enumerate(histories):
+            ids[i, :len(h)] = np.asarray(h, np.int64).astype(np.int32)
+        ids_d = torch.from_numpy(ids).to(self.dev)
+        lens_d = torch.tensor([len(h) for h in histories], dtype=torch.int32, device=self.dev)
+        rec_d = torch.from_numpy(recs.view(np.uint8).reshape(rows, ST.RECORD.itemsize).copy()).to(self.dev)
+        fin = np.zeros(rows, np.int32) if finished is None else np.ascontiguousarray(finished, np.int32).copy()
+        assert len(fin) == rows
+        fin_d = torch.from_numpy(fin).to(self.dev)
+        off_p = data_p = None
+        V = nbytes = 0
+        if table is not None:
+            off_d = torch.from_numpy(np.ascontiguousarray(table[0], np.int32)).to(self.dev)
+            data_d = torch.from_numpy(np.ascontiguousarray(table[1], np.uint8)).to(self.dev)
+            off_p, data_p, V, nbytes = off_d.data_ptr(), data_d.data_ptr(), off_d.numel() - 1, data_d.numel()
+        torch.cuda.synchronize()
+        check(self.ctx, self.L.aur_stop_rows(self.ctx, rows, ids_d.data_ptr(), stride, lens_d.data_ptr(), rec_d.data_ptr(), fin_d.data_ptr(),
+                                             int(batch_max_new), off_p, data_p, V, nbytes, self._stream()), "aur_stop_rows")
+        torch.cuda.synchronize()
+        return fin_d.cpu().numpy()
+
     def slot_sampling(self, slot0: int, recs: np.ndarray):
         """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_sampling records (`sampling.records`): staged in
         device memory and copied into the bank when the stream gets there - before the prefill / commit that picks the first token."""
@@ -1087,7 +1176,7 @@ class AuroraCapEngine:
 
     def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
                  sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None,
-                 logit_rules: Optional[dict] = None):
+                 logit_rules: Optional[dict] = None, stop=None):
         """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
         sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
         the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours.
@@ -1097,48 +1186,60 @@ class AuroraCapEngine:
         logit_rules=dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0), one dict for the call: transformers'
         three processors on the raw row ahead of the pick, greedy or sampled, as `aurora_amd.logit_rules` defines them - over the
         tokens GENERATED so far, never the prompt (what `generate(inputs_embeds=...)` gives the reference).  Log-probabilities stay
-        those of the unmodified row.  None or all-neutral values: exactly the path of a call without the argument."""
+        those of the unmodified row.  None or all-neutral values: exactly the path of a call without the argument.
+        stop=dict(token_ids=(), strings=(), max_new_tokens=0) for every sequence, or a list with one dict or None per sequence: a
+        sequence also ends behind a token that is one of its stop ids, behind one whose bytes complete one of its stop strings
+        (`set_stop_vocab` first), or when it holds its own max_new_tokens - decided on the device behind every pick, as
+        `aurora_amd.stopping` defines it; the token that stops it stays in the output and `stopping.finish_reason` names the reason
+        from the ids.  None or all-neutral records: exactly the path of a call without the argument."""
         lpn = check_logprobs(logprobs)
         B = len(embeds_list)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
+        stops = None if stop is None else self._stop_records(stop, B, max_new_tokens)
         if samp is not None:
             self._sampling_on()
         if rules is not None:
             self._rules_on()
+        if stops is not None:
+            self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         self._begin_rules(rules, B)
+        self._begin_stop(stops, B)
         for b in range(B):
             self.prefill(b, embeds_list[b], seq_lens[b])
+        may_end = eos_id is not None or stops is not None
         done = 1
         while done < max_new_tokens:
-            n = min(check_every, max_new_tokens - done) if eos_id is not None else max_new_tokens - done
+            n = min(check_every, max_new_tokens - done) if may_end else max_new_tokens - done
             self.decode(n)
             done += n
-            if eos_id is not None and self.unfinished() == 0:
+            if may_end and self.unfinished() == 0:
                 break
         return self.outputs(lpn)
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
                     eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None,
-                    logit_rules: Optional[dict] = None):
-        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules: as in
-        `generate`."""
+                    logit_rules: Optional[dict] = None, stop: Optional[dict] = None):
+        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules / stop: as
+        in `generate`."""
         check_logprobs(logprobs)
         LR.check_logit_rules(logit_rules)
+        if stop is not None:
+            self._stop_records(stop, 1, max_new_tokens)
         r = self.tome_r(token_kept_ratio, pixels.shape[-2], pixels.shape[-1])
         vis = self.vit_encode(pixels, r)
         emb, L = self.project_splice(vis, input_ids)
         return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream], logprobs=logprobs,
-                             logit_rules=logit_rules)[0]
+                             logit_rules=logit_rules, **({} if stop is None else dict(stop=stop)))[0]
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
                       streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None,
-                      logit_rules: Optional[dict] = None):
+                      logit_rules: Optional[dict] = None, stop=None):
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
@@ -1151,13 +1252,15 @@ class AuroraCapEngine:
         sibling whose prompt shares less than a page with the first clip's, or diverges from it before the visual rows end, takes the
         unshared path.  The same ids either way; share=None is exactly the path above.
         logprobs=n: a dict per clip instead of its ids, as in `generate`.
-        logit_rules: one dict for every clip of the call, as in `generate` (each clip's own generated tokens are its history)."""
+        logit_rules: one dict for every clip of the call, as in `generate` (each clip's own generated tokens are its history).
+        stop: one dict for every clip, or a list with one dict or None per clip, as in `generate`; siblings get theirs like any clip."""
         lpn = check_logprobs(logprobs)
         B = len(clips)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{B} clips for an engine built with max_batch={self.max_batch}")
+        stops = None if stop is None else self._stop_records(stop, B, max_new_tokens)
         if share is not None and len(share) != B:
             raise ValueError(f"{len(share)} share keys for {B} clips")
         d = self.l["hidden_size"]
@@ -1183,11 +1286,14 @@ class AuroraCapEngine:
             self._sampling_on()
         if rules is not None:
             self._rules_on()
+        if stops is not None:
+            self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         self._begin_rules(rules, B)
+        self._begin_stop(stops, B)
         runs, b0 = [], 0                                          # maximal runs of neighbouring clips that are nobody's sibling
         for i in range(B + 1):
             if i == B or i in child:
@@ -1225,24 +1331,26 @@ class AuroraCapEngine:
             self.kv_copy_prefix(p, i, g, fork)
             self.extend_batch(i, g, buf, fork, stride, new)
             i += g
+        may_end = eos_id is not None or stops is not None
         done = 1
         while done < max_new_tokens:
-            n = min(check_every, max_new_tokens - done) if eos_id is not None else max_new_tokens - done
+            n = min(check_every, max_new_tokens - done) if may_end else max_new_tokens - done
             self.decode(n)
             done += n
-            if eos_id is not None and self.unfinished() == 0:
+            if may_end and self.unfinished() == 0:
                 break
         return self.outputs(lpn)
 
     def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
                         eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None,
-                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None):
+                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None):
         """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
         (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs / logit_rules: as
-        in `generate`."""
+        in `generate`; stop: one dict for every prompt, or a list with one dict or None per prompt."""
         check_logprobs(logprobs)
         LR.check_logit_rules(logit_rules)
         prompts = [list(ids) for ids in list_of_input_ids]
+        stops = None if stop is None else self._stop_records(stop, len(prompts), max_new_tokens)
         st = list(range(len(prompts))) if streams is None else [int(x) for x in streams]
         out: List[List[int]] = []
         for c0 in range(0, len(prompts), self.max_batch):
@@ -1250,7 +1358,8 @@ class AuroraCapEngine:
             out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
                                       streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk),
                                       **({} if logprobs is None else dict(logprobs=logprobs)),
-                                      **({} if logit_rules is None else dict(logit_rules=logit_rules)))
+                                      **({} if logit_rules is None else dict(logit_rules=logit_rules)),
+                                      **({} if stops is None else dict(stop=stops[c0:c0 + len(chunk)])))
         return out
 
     # ------------------------------------------------------------------ continuous batching
@@ -1277,7 +1386,7 @@ class AuroraCapEngine:
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
                        sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None,
-                       logit_rules: Optional[dict] = None):
+                       logit_rules: Optional[dict] = None, stop=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -1304,14 +1413,27 @@ class AuroraCapEngine:
         logprobs=n: yields (index, dict) - ids, token_logprobs, top_ids, top_logprobs as in `generate` - in both modes, for clips
         from either front end.
         logit_rules: one dict for every clip of the call, as in `generate`; a re-filled slot gets its record where it gets its
-        sampling record, before its first token is picked, and its history starts empty."""
+        sampling record, before its first token is picked, and its history starts empty.
+        stop: one dict for every clip of the call, as in `generate`, or a callable index -> dict | None, called where `stream_of` is
+        (in the overlapped mode: when the clip's front end is prepared, so that a rejected record is the clip's own error).  A
+        request's own max_new_tokens frees its slot at the next check after it is reached.  A re-filled slot gets its record where
+        it gets its sampling and logit-rule records, in both modes and for sibling front ends too.  A callable counts as asking: the
+        option is flipped when the call starts, since front-end graphs cannot be dropped while clips are staged behind them."""
         lpn = check_logprobs(logprobs)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
+        stop_of = None
+        if callable(stop):
+            stop_of = lambda idx: ST.check_stop(stop(idx), max_new_tokens, self._stop_table)      # noqa: E731
+        elif stop is not None:
+            one = ST.check_stop(stop, max_new_tokens, self._stop_table)
+            stop_of = None if one is None else (lambda idx: one)
         if samp is not None:
             self._sampling_on()
         if rules is not None:
             self._rules_on()
+        if stop_of is not None:
+            self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
         B = self.max_batch if slots is None else slots
@@ -1327,7 +1449,7 @@ class AuroraCapEngine:
             if self.spare_slots - n_hold < 1:
                 raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1 beyond its prefix_cache")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph, samp, stream_of, share_key, holders, lpn, rules)
+                                                       front_graph, samp, stream_of, share_key, holders, lpn, rules, stop_of)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -1347,6 +1469,7 @@ class AuroraCapEngine:
                         r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
                         key = share_key(idx) if share_key is not None else None
                         hit = self._holder_hit(holders, key, px, list(ids), r) if key is not None else None
+                        srec = ST.records([stop_of(idx)]) if stop_of is not None else None      # validated before anything is enqueued
                         if hit is not None:                       # a sibling: pages from the holder, then the rows behind the fork
                             h, fork, buf, stride, new = hit
                             self.kv_copy_prefix(h["seq"], s, 1, fork)
@@ -1355,6 +1478,8 @@ class AuroraCapEngine:
                                 self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                             if rules is not None:
                                 self.slot_logit_rules(s, LR.records(rules, 1))
+                            if srec is not None:
+                                self.slot_stop(s, srec)
                             self.extend_batch(s, 1, buf, fork, stride, new)
                             owner[s] = idx
                             continue
@@ -1366,6 +1491,8 @@ class AuroraCapEngine:
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                         if rules is not None:
                             self.slot_logit_rules(s, LR.records(rules, 1))
+                        if srec is not None:
+                            self.slot_stop(s, srec)
                         self.prefill(s, emb, L)                   # argument checks come before any enqueue: a rejection leaves the slot idle
                         if key is not None:
                             self._holder_fill(holders, key, s, vis, plan, px, r)
@@ -1478,7 +1605,7 @@ class AuroraCapEngine:
         return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"]), fg
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
-                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None, rules=None):
+                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None, rules=None, stop_of=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -1490,7 +1617,7 @@ class AuroraCapEngine:
         n_hold = len(holders.free) if holders is not None else 0                       # the last spare sequences hold shared prefixes
         free_seqs = list(range(self.max_batch, self.max_batch + self.spare_slots - n_hold))     # spare KV sequences holding no prepared clip
         reusable = {}                                             # sequence -> event after which its (exchanged) pages may be rewritten
-        staged = deque()                                          # prepared clips: (index, sequence, embeds, L, event)
+        staged = deque()                                          # prepared clips: (index, sequence, embeds, L, event, stop record)
         exhausted = False
         sF.wait_stream(sD)
         self.set_option("gemm_max_wgs", 8 * front_cus)            # the persistent GEMM sizes its grid to the front end's CUs
@@ -1500,13 +1627,15 @@ class AuroraCapEngine:
                 # 1. slots that are free take over prepared clips (decode stream, between two decode calls)
                 for s in range(B):
                     if owner[s] is None and staged:
-                        idx, seq, emb, L, ev = staged.popleft()
+                        idx, seq, emb, L, ev, srec = staged.popleft()
                         sD.wait_event(ev)
                         emb.record_stream(sD)
                         if samp is not None:                      # the captured front end holds the stage only: the pick is the commit's
                             self.slot_sampling(s, S.records(samp, [idx if stream_of is None else stream_of(idx)]))
                         if rules is not None:                     # begin_batch made every slot neutral; a commit keeps a slot's record
                             self.slot_logit_rules(s, LR.records(rules, 1))
+                        if srec is not None:                      # a neutral record too: the commit keeps what the slot's last clip left
+                            self.slot_stop(s, srec)
                         if isinstance(L, tuple) and L[0] == "extend":     # a sibling staged behind a copied prefix: (_, fork, stride, rows)
                             L[3].record_stream(sD)
                             self.extend_commit(s, 1, seq, emb, L[1], L[2], L[3])
@@ -1556,6 +1685,7 @@ class AuroraCapEngine:
                             if seq in reusable:
                                 sF.wait_event(reusable.pop(seq))
                             r = self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1])
+                            srec = ST.records([stop_of(idx)]) if stop_of is not None else None
                             key = share_key(idx) if share_key is not None else None
                             hit = self._holder_hit(holders, key, px, list(ids), r) if key is not None else None
                             if hit is not None:                   # a sibling: no ViT, eager on this stream into its spare sequence
@@ -1579,7 +1709,7 @@ class AuroraCapEngine:
                                     self._holder_fill(holders, key, seq, vis, plan, px, r)
                             ev = torch.cuda.Event()
                             ev.record(sF)
-                        staged.append((idx, seq, emb, L, ev))
+                        staged.append((idx, seq, emb, L, ev, srec))
                     except (ValueError, IndexError, AssertionError, _lib.AuroraHipError) as e:
                         free_seqs.append(seq)
                         if on_error is None:

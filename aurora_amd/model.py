@@ -20,6 +20,7 @@ import torch
 
 from .engine import AuroraCapEngine
 from .logit_rules import KEYS as LOGIT_RULE_KEYS, check_logit_rules
+from . import stopping as ST
 from .sampling import DEFAULT_TOP_K, check_sampling
 from .scoring import check_logprobs
 
@@ -97,6 +98,20 @@ class GenerateOutput:
         self.sequences, self.token_logprobs, self.top_ids, self.top_logprobs = sequences, token_logprobs, top_ids, top_logprobs
 
 
+def split_stop_arguments(eos_token_id, stop_strings=None, stop_token_ids=None):
+    """transformers' keywords -> (the batch's EOS, a `stop=` dict or None): eos_token_id may be a list, whose first id is the EOS and
+    whose other ids are stop ids, in front of stop_token_ids; stop_strings may be one string."""
+    ids = []
+    if isinstance(eos_token_id, (list, tuple)):
+        eos_token_id, ids = (eos_token_id[0], list(eos_token_id[1:])) if len(eos_token_id) else (None, [])
+    ids += [] if stop_token_ids is None else list(stop_token_ids)
+    strings = [] if stop_strings is None else ([stop_strings] if isinstance(stop_strings, str) else list(stop_strings))
+    ids = [t for k, t in enumerate(ids) if t != eos_token_id and t not in ids[:k]]       # the EOS already stops; duplicates say nothing new
+    if not ids and not strings:
+        return eos_token_id, None
+    return eos_token_id, dict(token_ids=ids, strings=strings)
+
+
 class _LLM:
     def __init__(self, engine: AuroraCapEngine, eos_token_id: Optional[int]):
         self._e = engine
@@ -104,13 +119,21 @@ class _LLM:
         self.generation_top_k = None          # generation_config.json's top_k, when the checkpoint has one (AuroraModel.from_pretrained)
         self.generation_logit_rules = {}      # its repetition_penalty / no_repeat_ngram_size / min_new_tokens, those it sets
         self.config = engine.l
+        self._stop_tokenizer = None           # the tokenizer whose byte table the engine holds (use_tokenizer)
+
+    def use_tokenizer(self, tokenizer):
+        """Stop strings are matched on the bytes the tokens decode to: build the tokenizer's table (`stopping.token_bytes`) and hand
+        it to the engine, once per tokenizer."""
+        if tokenizer is not self._stop_tokenizer:
+            self._e.set_stop_vocab(ST.token_bytes(tokenizer, self.config.get("vocab_size")))
+            self._stop_tokenizer = tokenizer
 
     def generate(self, inputs_embeds: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.0, top_p: float = 1.0,
                  num_beams: int = 1, max_new_tokens: int = 2048, input_ids=None, position_ids=None, attention_mask=None,
                  past_key_values=None, labels=None, eos_token_id="default", top_k="default", seed: int = 0, stream: int = 0,
                  output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                 min_new_tokens: Optional[int] = None, **unused):
+                 min_new_tokens: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_ids=None, **unused):
         """do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
         sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
         passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
@@ -127,7 +150,13 @@ class _LLM:
         GENERATED so far, not the prompt - what transformers sees here too, since `generate(inputs_embeds=...)` starts `input_ids`
         empty.  None (the default): the value of the checkpoint's generation_config.json (`self.generation_logit_rules`) when it
         sets one, else off; an explicit argument wins.  Values transformers rejects raise ValueError.  Log-probabilities stay
-        those of the unmodified row."""
+        those of the unmodified row.
+        stop_strings=[...] with tokenizer=tok (transformers requires the tokenizer too; without it: ValueError): generation ends
+        behind the token whose text completes one of the strings, which stays in the output, as with transformers'
+        StopStringCriteria (`aurora_amd.stopping`).  eos_token_id may be a list: its first id is the EOS, the others - and
+        stop_token_ids - end the generation the same way, but `min_new_tokens` holds back the first alone."""
+        if stop_strings is not None and tokenizer is None:
+            raise ValueError("stop_strings needs tokenizer= as well: the strings are matched on the text the tokens decode to")
         if output_logprobs and not return_dict_in_generate:
             raise ValueError("output_logprobs=True needs return_dict_in_generate=True (the plain call returns the ids tensor alone)")
         lpn = check_logprobs(top_logprobs) if output_logprobs else None
@@ -145,6 +174,9 @@ class _LLM:
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
             raise ValueError(f"inputs_embeds must be [1, L, {self.config['hidden_size']}], got {tuple(inputs_embeds.shape)}")
         eos = self.eos_token_id if eos_token_id == "default" else eos_token_id
+        eos, stop = split_stop_arguments(eos, stop_strings, stop_token_ids)
+        if stop is not None and stop.get("strings"):
+            self.use_tokenizer(tokenizer)
         L, d = inputs_embeds.shape[1], inputs_embeds.shape[2]
         pad = torch.zeros((L + 31) // 32 * 32, d, dtype=torch.float16, device=self._e.dev)
         pad[:L] = inputs_embeds[0].to(device=self._e.dev, dtype=torch.float16)
@@ -152,6 +184,8 @@ class _LLM:
         kw = dict(sampling=sampling, streams=[stream]) if sampling else {}
         if rules is not None:
             kw["logit_rules"] = rules
+        if stop is not None:
+            kw["stop"] = stop
         if lpn is None:
             ids = self._e.generate([pad], [L], n, eos_id=eos, **kw)[0]
             seq = torch.tensor([ids], dtype=torch.long)
@@ -181,7 +215,7 @@ class AuroraModel:
         return model
 
     def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None,
-                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None):
+                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
@@ -190,13 +224,19 @@ class AuroraModel:
         of their common prefix inside a chunk of max_batch clips (AuroraCapEngine.caption_batch).
         logprobs=n (0 .. 8): a dict per clip instead - ids, token_logprobs, top_ids, top_logprobs (AuroraCapEngine.generate).
         logit_rules=dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0): the three rules of `llm.generate` for
-        every clip of the call, each over its own generated tokens (not its prompt)."""
+        every clip of the call, each over its own generated tokens (not its prompt).
+        stop=dict(token_ids=(), strings=(), max_new_tokens=0) for every clip, or a list with one dict or None per clip: stop ids,
+        stop strings (`llm.use_tokenizer(tok)` first) and a budget of the clip's own (AuroraCapEngine.generate)."""
         check_logprobs(logprobs)
         rules = check_logit_rules(logit_rules)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
         n = min(max_new_tokens, self.engine.max_new_tokens)
+        if stop is not None and not isinstance(stop, dict):
+            stop = list(stop)
+            if len(stop) != len(clips):
+                raise ValueError(f"{len(stop)} stop records for {len(clips)} clips")
         for c0 in range(0, len(clips), B):
             group = [(px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips[c0:c0 + B]]
             st = range(c0, c0 + len(group)) if streams is None else list(streams)[c0:c0 + len(group)]
@@ -207,6 +247,8 @@ class AuroraModel:
                 kw["logprobs"] = logprobs
             if rules is not None:
                 kw["logit_rules"] = rules
+            if stop is not None:
+                kw["stop"] = stop if isinstance(stop, dict) else stop[c0:c0 + len(group)]
             out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
         return out
 
@@ -221,13 +263,16 @@ class AuroraModel:
                                                self.visual_encoder.visual_token_merge_ratio, share=share)
 
     def caption_prompts(self, pixel_values, list_of_input_ids, max_new_tokens: int = 2048, eos_token_id="default", sampling=None,
-                        streams=None, logit_rules: Optional[dict] = None):
+                        streams=None, logit_rules: Optional[dict] = None, stop=None):
         """One clip, several prompts (the five VDC questions about a video): pixel_values [f, c, h, w], each prompt's input ids with
         -200 markers -> one new-token id list per prompt, in order, each identical to captioning (clip, prompt) alone.  The ViT runs
         once per chunk of max_batch prompts and the later prompts prefill only the rows behind the last visual token.  A slow-fast
-        model never shares: its prompts run one at a time through the three calls.  logit_rules: as in `caption_batch`."""
+        model never shares: its prompts run one at a time through the three calls.  logit_rules / stop: as in `caption_batch`
+        (a slow-fast model takes no stop records)."""
         rules = check_logit_rules(logit_rules)
         prompts = [ids.tolist() if torch.is_tensor(ids) else list(ids) for ids in list_of_input_ids]
+        if self.slowfast and stop is not None:
+            raise NotImplementedError("caption_prompts(stop=) on a slow-fast model")
         if self.slowfast:
             out, ratio = [], self.visual_encoder.visual_token_merge_ratio
             for k, ids in enumerate(prompts):
@@ -239,17 +284,20 @@ class AuroraModel:
             self.visual_encoder.reset_tome_r(ratio)
             return out
         return self.caption_batch([(pixel_values, ids) for ids in prompts], max_new_tokens, eos_token_id, sampling, streams,
-                                  share=[0] * len(prompts), **({} if rules is None else dict(logit_rules=rules)))
+                                  share=[0] * len(prompts), **({} if rules is None else dict(logit_rules=rules)),
+                                  **({} if stop is None else dict(stop=stop)))
 
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
-                       overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None):
+                       overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None, stop=None):
         """Continuous batching over an iterable of (pixel_values, input_ids): yields (index, new-token ids) as captions
         finish (EOS or max_new_tokens), re-filling freed KV slots with the next clips.  Per-clip results equal the
         one-at-a-time calls.  overlap (default: on for an engine with spare KV sequences): the next clips' front ends run
         ahead on a CU-masked stream while the slots decode (AuroraCapEngine.caption_stream).
         sampling=dict(temperature, top_k, top_p, seed): sampled captions; clip k draws with stream stream_of(k) (default: k).
         share_key: callable index -> key | None; clips of equal key are the same visual input (engine built with prefix_cache >= 1).
-        logit_rules: as in `caption_batch`; a clip's history starts empty in whatever slot it lands."""
+        logit_rules: as in `caption_batch`; a clip's history starts empty in whatever slot it lands.
+        stop: one dict for every clip, or a callable index -> dict | None (AuroraCapEngine.caption_stream): a clip with a budget of
+        its own gives its slot back when it is reached."""
         rules = check_logit_rules(logit_rules)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         n = min(max_new_tokens, self.engine.max_new_tokens)
@@ -258,7 +306,8 @@ class AuroraModel:
                                               on_error=on_error, overlap=overlap,
                                               **(dict(share_key=share_key) if share_key is not None else {}),
                                               **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}),
-                                              **(dict(logit_rules=rules) if rules is not None else {}))
+                                              **(dict(logit_rules=rules) if rules is not None else {}),
+                                              **(dict(stop=stop) if stop is not None else {}))
 
     def __call__(self, data: dict, data_samples=None, mode: str = "loss"):
         return self.forward(data, data_samples, mode)

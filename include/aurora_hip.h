@@ -238,6 +238,37 @@ typedef struct aur_logit_rules { float repetition_penalty; int32_t no_repeat_ngr
  * aur_begin_batch and aur_slot_reset set the slots they clear to neutral (the all-zero record: a penalty <= 0 counts as 1, like
  * (1, 0, 0)): such a slot's row is never touched.  A commit keeps a slot's record. */
 int aur_slot_logit_rules(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_logit_rules* rules_dev, void* stream);
+/* Stop conditions behind the pick: with option "stop_rules" = 1 (aur_set_option) stop_check_kernel runs behind
+ * every prefill's / commit's / decode step's pick, greedy or sampled, eager or captured, and sets finished[b] of an unfinished slot whose
+ * newest token t = h[n - 1] (h = the n tokens the slot has GENERATED, never the prompt) fulfils one of
+ *   stop_token: t is one of token_ids[0 .. n_token_ids);
+ *   stop_string: in the concatenation of the bytes the tokens of h decode to (the table of aur_stop_vocab), an occurrence of one of
+ *     strings[i][0 .. string_len[i]) ends inside t's bytes or at their end (it may begin in earlier tokens, t may go on behind it); a
+ *     token of zero bytes completes nothing, an id outside the table has no bytes and breaks the text;
+ *   length: n >= max_new_tokens (<= 0: the batch's limit alone, which advance_tail enforces in the engine).
+ * Nothing else is written: t stays in the output, and pos, the next-token embedding and out_len are what an EOS leaves, so a stopped slot
+ * behaves in later steps exactly like one that saw the EOS.  The kernel clamps n_token_ids / n_strings into [0, 8] and string_len into
+ * [0, 64] (a string of length 0 matches nothing); the all-zero record is neutral.  aurora_amd/stopping.py is the definition. */
+#define AUR_STOP_MAX_IDS 8
+#define AUR_STOP_MAX_STRINGS 8
+#define AUR_STOP_MAX_STRING_BYTES 64
+#define AUR_STOP_MAX_TOKEN_BYTES 255
+typedef struct aur_stop_rules {
+    int32_t max_new_tokens, n_token_ids, n_strings, reserved;
+    int32_t token_ids[AUR_STOP_MAX_IDS];
+    int32_t string_len[AUR_STOP_MAX_STRINGS];
+    uint8_t strings[AUR_STOP_MAX_STRINGS][AUR_STOP_MAX_STRING_BYTES];
+} aur_stop_rules;
+/* The bytes each vocabulary entry decodes to: offsets_dev int32 [vocab + 1] (entry t is bytes_dev[offsets[t] .. offsets[t + 1])), bytes_dev
+ * uint8 [nbytes]; caller-owned DEVICE memory that must outlive its use, handed over once (NULL, NULL, 0, 0 takes it back: string stops then
+ * match nothing).  The kernel never reads outside [0, vocab] / [0, nbytes) whatever the offsets hold, and a token counts at most 255 bytes.
+ * The pointers are frozen inside captured graphs: the decode graphs are dropped; AUR_ERR_STATE inside a capture. */
+int aur_stop_vocab(aur_ctx* ctx, const int32_t* offsets_dev, const uint8_t* bytes_dev, int32_t vocab, int64_t nbytes);
+/* per-slot records of the selected bank: aur_slot_sampling's contract - device-to-device from caller-owned DEVICE memory, enqueue-only,
+ * recordable; a capture freezes the pointer, not the values; ordered before the prefill / commit that picks the slot's first token.
+ * aur_begin_batch and aur_slot_reset set the slots they clear to neutral; a commit keeps a slot's record.  The records live in memory the
+ * first "stop_rules" 1 allocates (aur_workspace_bytes does not grow): AUR_ERR_STATE before that. */
+int aur_slot_stop(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_stop_rules* rules_dev, void* stream);
 /* Run `steps` decode steps for slots [0, batch): one new token per unfinished slot per step. */
 int aur_llm_decode(aur_ctx* ctx, int32_t steps, void* stream);
 /* Synchronises the stream and copies results to host: ids [batch * max_new_tokens], lens [batch]. */
@@ -377,6 +408,13 @@ int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t voc
  * its input again.  Allocates its side list, synchronises the stream and frees it: not recordable. */
 int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const int32_t* ids_dev, int32_t ids_stride,
                          const int32_t* lens_dev, const aur_logit_rules* rules_dev, int32_t eos_id, int32_t restore, void* stream);
+/* stop_check_kernel alone on caller rows (parity tests).  ids_dev int32 [rows, ids_stride] and lens_dev int32 [rows]: row i's generated
+ * tokens are ids_dev[i][0 .. min(lens_dev[i], ids_stride)); rules_dev [rows] (8-byte aligned); finished_dev int32 [rows], read and written:
+ * a row whose flag is set is skipped, a row that stops gets 1; batch_max_new: the limit a record with max_new_tokens <= 0 stands for
+ * and that ends a row on its own, as advance_tail does in the engine.  The byte table as aur_stop_vocab takes it (NULL: no string
+ * matches).  Enqueue-only. */
+int aur_stop_rows(aur_ctx* ctx, int32_t rows, const int32_t* ids_dev, int32_t ids_stride, const int32_t* lens_dev, const aur_stop_rules* rules_dev,
+                  int32_t* finished_dev, int32_t batch_max_new, const int32_t* offsets_dev, const uint8_t* bytes_dev, int32_t vocab, int64_t nbytes, void* stream);
 
 /* ---- scoring given continuations (lmms-eval's `loglikelihood` request) ---------------------------------------
  * aur_score_rows: the kernel alone on caller rows.  logits fp32 [rows, vocab] device; targets_dev int32 [rows].  Per row, with a =
@@ -446,7 +484,9 @@ int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int3
  * row in LDS when it fits) / 0 (re-reads it from L2; same tokens), "logit_rules" 0 (default: the launches are exactly those of a ctx
  * that never heard of them) / 1 (logit_rules_apply_kernel ahead of every pick and logit_rules_restore_kernel behind it, with the slots'
  * aur_logit_rules records; frozen inside captured graphs exactly like "sampling"; the first 1 allocates the banks' side lists -
- * max_batch * (max_new_tokens + 1) entries of 8 bytes each - which live as long as the ctx).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
+ * max_batch * (max_new_tokens + 1) entries of 8 bytes each - which live as long as the ctx), "stop_rules" 0 (default: the launches are exactly those of a ctx that never
+ * heard of it) / 1 (stop_check_kernel behind every pick, with the slots' aur_stop_rules records; frozen inside captured graphs exactly like
+ * "sampling"; the first 1 allocates the banks' records - max_batch * sizeof(aur_stop_rules) each - which live as long as the ctx).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
  * launch) / 0 (its own launch; bitwise the same); "prefill_prune_last" 1 (default) / 0: the last layer of a prefill computes K / V for
  * every position and the rest for each sequence's last 128 rows only - nothing else is read after it; bitwise the same logits and K / V;
  * "decode_half_grid" 1 / 0 (one graph is kept per setting): the next aur_llm_decode calls go to a stream that owns half of the CUs, so
@@ -462,7 +502,7 @@ int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int3
  * LDS above; mk_skinny in aurora_amd/csrc/engine.hip is the one place that picks it, for the step, aur_microbench and the parity entries), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
 int aur_set_option(aur_ctx* ctx, const char* name, int64_t value);
 /* Time one kernel of the LLM path in isolation on the current generation state (after aur_llm_prefill):
- * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), pre_norm, pre_qkv, pre_attn,
+ * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), dec_stop (stop_check_kernel; option "stop_rules" 1), pre_norm, pre_qkv, pre_attn,
  * pre_o, pre_gateup, pre_down}; mean microseconds per launch over `iters` launches cycling through the layers. */
 int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, double* us_out, void* stream);
 

@@ -46,6 +46,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--no_repeat_ngram_size', type=int, default=None, help='no n-gram of this size occurs twice in the generated tokens (0 = off)')
     parser.add_argument('--min_new_tokens', type=int, default=None, help='the EOS token cannot be picked before this many tokens (0 = off)')
     # more questions about the same input: the vision tower runs once and the later prompts prefill only the rows behind the last visual token
+    parser.add_argument('--stop', action='append', default=[], metavar='STR',
+                        help='end the caption behind the token that completes this text (repeatable, at most 8 of up to 64 bytes); the text '
+                             'stays in the printed caption')
+    parser.add_argument('--stop_token_id', action='append', type=int, default=[], metavar='N',
+                        help='end the caption behind this token id (repeatable, at most 8)')
     parser.add_argument('--extra_prompt', action='append', default=[], metavar='TEXT',
                         help='a further instruction about the same visual input (repeatable): one more caption is printed per flag, in order; '
                              'with --synthetic there is no tokenizer: the text is ignored and each flag adds a seeded prompt of its own length')
@@ -86,6 +91,15 @@ def main():
         check_logit_rules(rule_args)
     except ValueError as e:
         sys.exit(f"error: {e}")
+    try:
+        from aurora_amd.stopping import check_stop
+        stop = check_stop(dict(strings=args.stop, token_ids=args.stop_token_id), need_table=False)
+    except ValueError as e:
+        sys.exit(f"error: {e}")
+    if args.stop and args.synthetic:
+        sys.exit("error: --stop matches text and needs a checkpoint's tokenizer (--synthetic has none); --stop_token_id works without one")
+    if stop is not None and args.score is not None:
+        sys.exit("error: --stop / --stop_token_id go with generated captions (not with --score)")
     if args.num_beams != 1:
         sys.exit("error: beam search is not implemented on the MI355X path: generation is greedy or, with --do_sample, sampled (--num_beams 1)")
 
@@ -169,8 +183,10 @@ def main():
     if extra_ids:                     # several prompts about one input: one caption per prompt, in order
         px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
         samp = dict(temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=args.seed) if args.do_sample else None
+        if args.stop:
+            model.llm.use_tokenizer(tokenizer)
         outs = model.caption_prompts(px, [data["input_ids"][0].tolist()] + extra_ids, max_new_tokens=args.max_new_tokens, sampling=samp,
-                                     **(dict(logit_rules=rule_args) if rule_args else {}))
+                                     **(dict(logit_rules=rule_args) if rule_args else {}), **(dict(stop=stop) if stop is not None else {}))
         for ids in outs:
             print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
         return
@@ -178,6 +194,8 @@ def main():
     sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
     cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
                               num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample, **rule_args,
+                              **(dict(stop_strings=args.stop, tokenizer=tokenizer) if args.stop else {}),
+                              **(dict(stop_token_ids=args.stop_token_id) if args.stop_token_id else {}),
                               **(dict(return_dict_in_generate=True, output_logprobs=True, top_logprobs=args.logprobs)
                                  if args.logprobs is not None else {}))
     lp_out = None
