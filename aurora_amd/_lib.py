@@ -17,6 +17,9 @@ AUR_ACT_GELU = 2
 AUR_ACT_SILU = 4
 AUR_ACT_RELU = 5
 AUR_ACT_GELU_TANH = 6
+AUR_GEMM_SILU_MUL = 3               # aur_gemm_rows only: silu(gate) * up over interleaved columns
+# aur_gemm_rows: which projection's instantiation of the 256x256 kernel runs
+GEMM_TAGS = {"other": 0, "vit_out": 2, "vit_fc1": 3, "vit_fc2": 4, "llm_o": 6, "llm_gateup": 7, "llm_down": 8}
 # transformers' ACT2FN names (modeling_projector.py:27 `ACT2FN[config.hidden_act]`) the kernels' epilogues implement; anything else raises
 ACT_BY_NAME = {"quick_gelu": AUR_ACT_QUICK_GELU, "gelu": AUR_ACT_GELU, "silu": AUR_ACT_SILU, "swish": AUR_ACT_SILU, "relu": AUR_ACT_RELU,
                "gelu_new": AUR_ACT_GELU_TANH, "gelu_pytorch_tanh": AUR_ACT_GELU_TANH}
@@ -108,6 +111,7 @@ SIGNATURES = {
     "aur_decode_stamps_read": (C.c_int, [_P, C.POINTER(C.c_double), _I, C.POINTER(_L), _IP, _P]),
     "aur_tome_step": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "aur_linear": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "aur_gemm_rows": (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P]),
     "aur_linear_skinny": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "aur_layernorm": (C.c_int, [_P, _P, _I, _I, _P, _P, C.c_float, _P, _P]),
     "aur_rmsnorm": (C.c_int, [_P, _P, _I, _I, _P, C.c_float, _P, _P]),

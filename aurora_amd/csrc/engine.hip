@@ -885,15 +885,49 @@ static SkinnyArgs mk_skinny(const aur_ctx* ctx, int mode, const half_t* xf, cons
 }
 
 // ------------------------------------------------------------------------------------------ generic ops
+static_assert(AUR_GEMM_SILU_MUL == ACT_SILU_MUL && AUR_ACT_SILU == ACT_SILU && AUR_ACT_RELU == ACT_RELU && AUR_ACT_GELU_TANH == ACT_GELU_TANH, "public activation codes");
+static_assert(AUR_GEMM_TAG_OTHER == GT_OTHER && AUR_GEMM_TAG_VIT_OUT == GT_VIT_OUT && AUR_GEMM_TAG_VIT_FC1 == GT_VIT_FC1 && AUR_GEMM_TAG_VIT_FC2 == GT_VIT_FC2 &&
+              AUR_GEMM_TAG_LLM_O == GT_LLM_O && AUR_GEMM_TAG_LLM_GATEUP == GT_LLM_GATEUP && AUR_GEMM_TAG_LLM_DOWN == GT_LLM_DOWN, "public GEMM tags");
+// One EPI_ROW launch on caller buffers: every rule the two tile kernels and their epilogues assume is checked HERE, before anything is
+// launched (aur_gemm_rows in include/aurora_hip.h says where each one comes from); aur_linear is the same launch with lda = k,
+// ldc = ldr = n, no tag and no row map.
+static int gemm_rows(aur_ctx* ctx, const char* who, const void* a, int m, int k, int lda, const void* w_packed, int npad, int n, const float* bias,
+                     int act, int tag, const void* resid, int ldr, const int32_t* out_rows, void* c, int ldc, hipStream_t s) {
+    if (!ctx) return AUR_ERR_ARG;
+    if (!a || !w_packed || !c) return aur_fail(ctx, AUR_ERR_ARG, "%s: null argument", who);
+    if (m < 1 || k < 64 || (k & 63) || npad < 128 || (npad & 127) || n < 4 || n > npad || (n & 3))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: need m >= 1, k a positive multiple of 64, npad a positive multiple of 128, n %% 4 == 0, 4 <= n <= npad (got %d, %d, %d, %d)", who, m, k, npad, n);
+    if (act != ACT_NONE && act != ACT_QUICK_GELU && act != ACT_GELU && act != ACT_SILU_MUL && act != ACT_SILU && act != ACT_RELU && act != ACT_GELU_TANH)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: act %d is neither 0, an AUR_ACT_* nor AUR_GEMM_SILU_MUL", who, act);
+    if (tag != GT_OTHER && tag != GT_VIT_OUT && tag != GT_VIT_FC1 && tag != GT_VIT_FC2 && tag != GT_LLM_O && tag != GT_LLM_GATEUP && tag != GT_LLM_DOWN)
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: tag %d is not an AUR_GEMM_TAG_* of a row-major projection", who, tag);
+    if (lda < k || (lda & 7) || ((uintptr_t)a & 15) || ((uintptr_t)w_packed & 15))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: need lda >= k, lda %% 8 == 0, a and w_packed 16-byte aligned (lda %d, k %d)", who, lda, k);
+    const bool mul = act == ACT_SILU_MUL;
+    const int stored = mul ? n / 2 : n;
+    if (ldc < stored || (ldc & (mul ? 1 : 3)) || ((uintptr_t)c & 15))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: need ldc >= %d stored columns, ldc %% %d == 0, c 16-byte aligned (ldc %d)", who, stored, mul ? 2 : 4, ldc);
+    if (resid) {
+        if (mul) return aur_fail(ctx, AUR_ERR_ARG, "%s: the gate-times-up mode takes no residual", who);
+        if (ldr < n || (ldr & 3) || ((uintptr_t)resid & 15)) return aur_fail(ctx, AUR_ERR_ARG, "%s: need ldr >= n, ldr %% 4 == 0, resid 16-byte aligned (ldr %d, n %d)", who, ldr, n);
+        if (resid == c && (ldr != ldc || out_rows)) return aur_fail(ctx, AUR_ERR_ARG, "%s: a residual read in place needs ldr == ldc and no row map", who);
+    }
+    GemmArgs g{};
+    g.A = (const half_t*)a; g.lda = lda; g.W = (const half_t*)w_packed; g.bias = bias; g.M = m; g.Npad = npad; g.K = k;
+    g.C = (half_t*)c; g.ldc = ldc; g.resid = (const half_t*)resid; g.ldr = ldr; g.n_real = n; g.out_rows = out_rows;
+    g.act = act; g.tag = tag;
+    CK(ctx_gemm(ctx, g, EPI_ROW, s));
+    return AUR_OK;
+}
 extern "C" int aur_linear(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad, int32_t n,
                           const float* bias, int32_t act, const void* resid, void* c, void* stream) {
-    if (m < 1 || (k & 63) || (npad & 127) || n > npad || (n & 3)) return aur_fail(ctx, AUR_ERR_ARG, "aur_linear: need k %% 64 == 0, npad %% 128 == 0, n %% 4 == 0");
-    GemmArgs g{};
-    g.A = (const half_t*)a; g.lda = k; g.W = (const half_t*)w_packed; g.bias = bias; g.M = m; g.Npad = npad; g.K = k;
-    g.C = (half_t*)c; g.ldc = n; g.resid = (const half_t*)resid; g.ldr = n; g.n_real = n;
-    g.act = act == AUR_ACT_GELU ? ACT_GELU : act == AUR_ACT_QUICK_GELU ? ACT_QUICK_GELU : ACT_NONE;
-    CK(ctx_gemm(ctx, g, EPI_ROW, (hipStream_t)stream));
-    return AUR_OK;
+    const int ga = act == AUR_ACT_GELU ? ACT_GELU : act == AUR_ACT_QUICK_GELU ? ACT_QUICK_GELU : ACT_NONE;
+    return gemm_rows(ctx, "aur_linear", a, m, k, k, w_packed, npad, n, bias, ga, GT_OTHER, resid, n, nullptr, c, n, (hipStream_t)stream);
+}
+extern "C" int aur_gemm_rows(aur_ctx* ctx, const void* a, int32_t m, int32_t k, int32_t lda, const void* w_packed, int32_t npad, int32_t n,
+                             const float* bias, int32_t act, int32_t tag, const void* resid, int32_t ldr, const int32_t* out_rows_dev, void* c,
+                             int32_t ldc, void* stream) {
+    return gemm_rows(ctx, "aur_gemm_rows", a, m, k, lda, w_packed, npad, n, bias, act, tag, resid, ldr, out_rows_dev, c, ldc, (hipStream_t)stream);
 }
 extern "C" int aur_linear_skinny(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                                  int32_t n, float* out, void* stream) {

@@ -1798,6 +1798,33 @@ class AuroraCapEngine:
         torch.cuda.synchronize()
         return out
 
+    def gemm_rows(self, a: torch.Tensor, w_packed: torch.Tensor, n: int, c: torch.Tensor, *, m: Optional[int] = None, k: Optional[int] = None,
+                  ldc: Optional[int] = None, bias: Optional[torch.Tensor] = None, act: int = 0, tag: int = 0, resid: Optional[torch.Tensor] = None,
+                  in_place: bool = False, out_rows=None) -> torch.Tensor:
+        """aur_gemm_rows: one EPI_ROW tile-GEMM launch on caller buffers.  a fp16 [rows, lda]: the operand is its first `m` rows (default
+        all; later rows are the caller's guard) by its first `k` columns (default all).  w_packed [npad, k] from `pack`; bias fp32 [npad].
+        `c` is the INITIAL content of the output - sentinels outside the stored set survive - with rows `ldc` halves apart (default: its
+        width; a flat tensor carries a guard behind the last row).  resid fp16 [rows >= m, ldr], or in_place: read from c itself.
+        out_rows: int32 [m], list or device tensor.  Returns the device copy of c as it is after the launch."""
+        ah = self._h(a)
+        m = ah.shape[0] if m is None else m
+        lda = ah.shape[1]
+        k = lda if k is None else k
+        npad = w_packed.numel() // k
+        ldc = c.shape[-1] if ldc is None else ldc
+        o = self._h(c).clone()
+        rh = self._h(resid) if resid is not None else None
+        rows_t = self._i32_arg(out_rows, m, "out_rows") if out_rows is not None else None
+        b = self._f(bias) if bias is not None else None
+        if b is not None and b.numel() < npad:
+            raise ValueError(f"bias of {b.numel()} entries for npad {npad}")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        check(self.ctx, self.L.aur_gemm_rows(self.ctx, ah.data_ptr(), m, k, lda, w_packed.data_ptr(), npad, n, ptr(b), act, tag,
+                                             o.data_ptr() if in_place else ptr(rh), ldc if in_place else (rh.shape[1] if rh is not None else 0),
+                                             ptr(rows_t), o.data_ptr(), ldc, self._stream()), "aur_gemm_rows")
+        torch.cuda.synchronize()
+        return o
+
     def linear_skinny(self, a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         n, k = w.shape
         npad = _rup(n, 256)

@@ -329,9 +329,45 @@ int aur_tome_step(aur_ctx* ctx, const float* metric, const void* x, const float*
                   int32_t* node_idx, int32_t* unm_idx, int32_t* src_idx, int32_t* dst_idx, void* stream);
 
 /* C[M, n] = act(A[M, K] W^T + bias) (+ resid): replaces F.linear.  w_packed from aur_pack_linear
- * (npad % 128 == 0, K % 64 == 0); bias fp32 [npad] or NULL; act 0 / AUR_ACT_*; resid fp16 [M, n] or NULL. */
+ * (npad % 128 == 0, K % 64 == 0, K >= 64, n % 4 == 0, 4 <= n <= npad: the rules of aur_gemm_rows at lda = K, ldc = ldr = n); bias fp32
+ * [npad] or NULL; act 0 / AUR_ACT_GELU / AUR_ACT_QUICK_GELU (any other value: none); resid fp16 [M, n] or NULL. */
 int aur_linear(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                int32_t n, const float* bias, int32_t act, const void* resid, void* c, void* stream);
+/* One row-major tile GEMM alone on caller buffers (tests/test_gpu_gemm_modes.py): a single EPI_ROW launch through the ctx's own
+ * dispatch, so "gemm_mode", "gemm_max_wgs", "gemm_tail_split" and "gemm_nt_out" apply exactly as they do to a prefill, ViT or projector
+ * GEMM, with every argument aur_linear fixes exposed:
+ *   a fp16, rows lda halves apart (a column window of a wider buffer when lda > k); w_packed [npad, k] from aur_pack_linear;
+ *   bias fp32 [npad] (ALL npad entries are read: the 256x256 kernel's wide epilogue loads a tile's 64 bias columns unconditionally) or NULL;
+ *   act 0, an AUR_ACT_*, or AUR_GEMM_SILU_MUL: columns (2j, 2j + 1) of the product are (gate_j, up_j) - the weight packed with the
+ *     loader's interleaving row map - and silu(gate_j) * up_j is stored at column j: n is the interleaved width, n / 2 columns are stored;
+ *   tag AUR_GEMM_TAG_*: which projection's instantiation of the 256x256 kernel runs (its activation is a compile-time constant; a tag
+ *     whose activation is not `act` runs AUR_GEMM_TAG_OTHER); no effect on the result;
+ *   resid fp16, rows ldr halves apart, or NULL: added after the activation; may be c itself (then ldr == ldc and no row map);
+ *   out_rows_dev int32 [m] in device memory or NULL: row i of the product is stored at row out_rows_dev[i] of c, a negative entry drops
+ *     the row (the caller's promise that the rows exist and differ: the host never reads the array);
+ *   c fp16, rows ldc halves apart: only the stored columns of the stored rows are written.
+ * Refused with AUR_ERR_ARG before anything is launched (the ctx stays usable) - each rule is an access width of the kernels:
+ *   k % 64 == 0, k >= 64         a K-tile is 64 columns, and both kernels stage K-tile 0 unconditionally (gemm.hip, gemm256.hip prologue)
+ *   npad % 128 == 0              whole 128-column tiles of packed weight fragments (the 256x256 kernel needs npad % 256 == 0: else the 128 one runs)
+ *   n % 4 == 0, 4 <= n <= npad   a lane owns 4 consecutive columns: 8-byte h4 stores, and the residual load's column clamp is n - 4 (gemm_epilogue.h)
+ *   lda >= k, lda % 8 == 0       A rows are staged by 16-byte LDS-DMA pieces; a, w_packed 16-byte aligned for the same reason
+ *   ldc >= stored columns, ldc % 4 == 0 (% 2 with AUR_GEMM_SILU_MUL)     h4 (h2) stores of the direct epilogue; ldc % 8 == 0 (% 4) selects the
+ *                                256x256 kernel's wide epilogue with its 16-byte (8-byte) stores, hence c 16-byte aligned
+ *   ldr >= n, ldr % 4 == 0       h4 residual loads (16-byte ones in the wide epilogue when ldr % 8 == 0: resid 16-byte aligned)
+ *   no residual with AUR_GEMM_SILU_MUL (the epilogues ignore it, the wide one after loading n columns of it)
+ *   resid == c with ldr != ldc or a row map (a lane must read exactly the elements it later writes)
+ *   a tag outside the list below (the QKV tags belong to the other epilogue), an act outside the list. */
+#define AUR_GEMM_SILU_MUL 3
+#define AUR_GEMM_TAG_OTHER 0
+#define AUR_GEMM_TAG_VIT_OUT 2
+#define AUR_GEMM_TAG_VIT_FC1 3
+#define AUR_GEMM_TAG_VIT_FC2 4
+#define AUR_GEMM_TAG_LLM_O 6
+#define AUR_GEMM_TAG_LLM_GATEUP 7
+#define AUR_GEMM_TAG_LLM_DOWN 8
+int aur_gemm_rows(aur_ctx* ctx, const void* a, int32_t m, int32_t k, int32_t lda, const void* w_packed, int32_t npad, int32_t n,
+                  const float* bias, int32_t act, int32_t tag, const void* resid, int32_t ldr, const int32_t* out_rows_dev, void* c,
+                  int32_t ldc, void* stream);
 /* Same contraction through the decode weight-streaming kernel (m <= 128, k % 128 == 0, any n <= npad); out fp32 [m, n]. */
 int aur_linear_skinny(aur_ctx* ctx, const void* a, int32_t m, int32_t k, const void* w_packed, int32_t npad,
                       int32_t n, float* out, void* stream);
