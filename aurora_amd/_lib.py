@@ -82,6 +82,7 @@ SIGNATURES = {
     "aur_vit_encode": (C.c_int, [_P, _P, _I, _I, _P, _IP, _P]),
     "aur_vit_pos_interp": (C.c_int, [_P, _I, _I, _P, _P]),
     "aur_vit_encode_hw": (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _P, _IP, _P]),
+    "aur_vit_encode_map": (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _IP, _P]),
     "aur_project_splice": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "aur_project_splice_var": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "aur_begin_batch": (C.c_int, [_P, _I, _I, _I, _P]),
@@ -110,6 +111,8 @@ SIGNATURES = {
     "aur_graph_destroy": (C.c_int, [_P, _I]),
     "aur_decode_stamps_read": (C.c_int, [_P, C.POINTER(C.c_double), _I, C.POINTER(_L), _IP, _P]),
     "aur_tome_step": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "aur_tome_map_rows": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "aur_unmerge_rows": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "aur_linear": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "aur_gemm_rows": (C.c_int, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P]),
     "aur_linear_skinny": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),

@@ -3,6 +3,7 @@
 // Pipelines restate the reference's call sequence for the AuroraCap inference path with one enqueue per
 // kernel on the caller's stream:
 //   aur_vit_encode      <- AuroraEncoder.forward + AuroraCLIPEncoder loop   (aurora.py:883-904, 772-860, 713-759)
+//   aur_vit_encode_map  <- the same with merge_source carried through the layers (tome.py:222-232)
 //   aur_project_splice  <- projector + prepare_inputs_labels_for_multimodal (aurora.py:254-258, utils.py:138-295)
 //   aur_llm_prefill / aur_llm_decode <- LlamaForCausalLM.generate greedy    (inference.py:89-96)
 #include <dlfcn.h>
@@ -674,7 +675,8 @@ static KvLayout vit_kv(const aur_ctx* c, int t_pad) {
 // One encoder layer on padded state x [F][t_pad][D] (in place for r == 0; x_out otherwise).  Returns via
 // *t_out the new token count; result lives in *x_res / *size_res (one of the two ping-pong buffers).
 static int vit_layer_run(aur_ctx* ctx, int l, int F, int t, int r, half_t* x, const float* size, half_t* x_alt, float* size_alt,
-                         half_t** x_res, const float** size_res, int* t_out, hipStream_t s, bool want_metric = false) {
+                         half_t** x_res, const float** size_res, int* t_out, hipStream_t s, bool want_metric = false,
+                         int32_t* map = nullptr, int map_n = 0) {
     const aur_config& g = ctx->cfg;
     const VitLayerW& w = ctx->vl[l];
     const int D = g.vit_hidden, t_pad = rup(t, 32), M = F * t_pad;
@@ -711,6 +713,8 @@ static int vit_layer_run(aur_ctx* ctx, int l, int F, int t, int r, half_t* x, co
         if (ctx->prof) kev_begin(ctx->kev[2], s);
         CK(launch_tome_step(ta, s));                                                       // aurora.py:746-747
         if (ctx->prof) kev_end(ctx->kev[2], s);
+        // the merge map follows the step in a launch of its own: w_unm / w_src / w_dst are the next layer's too (merge_map.py)
+        if (map) CK(launch_tome_map(map, F, map_n, t, rl, ctx->w_unm, ctx->w_src, ctx->w_dst, s));
         xc = x_alt;
         sc = size_alt;
     }
@@ -742,8 +746,9 @@ extern "C" int aur_vit_pos_interp(aur_ctx* ctx, int32_t height, int32_t width, v
     return AUR_OK;
 }
 
-extern "C" int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t height, int32_t width,
-                                 const void* pos_emb, int32_t r, void* out_tokens, int32_t* n_kept_out, void* stream) {
+extern "C" int aur_vit_encode_map(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t height, int32_t width,
+                                  const void* pos_emb, int32_t r, void* out_tokens, int32_t* map_out, float* size_out,
+                                  int32_t* n_kept_out, void* stream) {
     if (!ctx->finalized || ctx->vl.empty()) return aur_fail(ctx, AUR_ERR_STATE, "aur_vit_encode: vision weights not finalized");
     const aur_config& g = ctx->cfg;
     if (frames < 1 || frames > g.max_frames) return aur_fail(ctx, AUR_ERR_ARG, "frames %d outside [1, %d]", frames, g.max_frames);
@@ -769,11 +774,13 @@ extern "C" int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frame
     const float* size = nullptr;          // aurora.py:811: size = None at layer 0
     float* size_alt = ctx->w_sza;
     int t = t0;
+    // the merge map is built in map_out itself: 1 + p, one rewrite behind every merging layer, the class row taken off at the end
+    if (map_out) CK(launch_tome_map_init(map_out, frames, npatch, s));
     for (int l = 0; l < g.vit_layers - 1; ++l) {
         half_t* xr;
         const float* sr;
         int t2;
-        int rc = vit_layer_run(ctx, l, frames, t, r, x, size, x_alt, size_alt, &xr, &sr, &t2, s);
+        int rc = vit_layer_run(ctx, l, frames, t, r, x, size, x_alt, size_alt, &xr, &sr, &t2, s, false, map_out, npatch);
         if (rc) return rc;
         if (xr != x) {           // merged into the alternate buffer: swap ping-pong roles
             x_alt = x;
@@ -784,9 +791,16 @@ extern "C" int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frame
         t = t2;
     }
     CK(launch_strip_cls(x, frames, t, rup(t, 32), D, (half_t*)out_tokens, s));           // aurora.py:253
+    // size stays null when no layer merged (r = 0): the sizes are then written as ones
+    if (map_out || size_out) CK(launch_tome_map_finish(map_out, frames, npatch, size, rup(t, 32), t - 1, size_out, s));
     if (n_kept_out) *n_kept_out = t - 1;
     stage_end(ctx, "vit", s);
     return AUR_OK;
+}
+
+extern "C" int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t height, int32_t width,
+                                 const void* pos_emb, int32_t r, void* out_tokens, int32_t* n_kept_out, void* stream) {
+    return aur_vit_encode_map(ctx, pixels, frames, height, width, pos_emb, r, out_tokens, nullptr, nullptr, n_kept_out, stream);
 }
 
 extern "C" int aur_vit_encode(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t r, void* out_tokens,
@@ -856,6 +870,28 @@ extern "C" int aur_tome_step(aur_ctx* ctx, const float* metric, const void* x, c
     if (unm_idx) CK(hipMemcpyAsync(unm_idx, ctx->w_unm, (size_t)frames * (ta - rl) * 4, hipMemcpyDeviceToDevice, s));
     if (src_idx) CK(hipMemcpyAsync(src_idx, ctx->w_src, (size_t)frames * rl * 4, hipMemcpyDeviceToDevice, s));
     if (dst_idx) CK(hipMemcpyAsync(dst_idx, ctx->w_dst, (size_t)frames * rl * 4, hipMemcpyDeviceToDevice, s));
+    return AUR_OK;
+}
+
+extern "C" int aur_tome_map_rows(aur_ctx* ctx, int32_t* rows_dev, int32_t frames, int32_t n, int32_t t, int32_t r, const int32_t* unm,
+                                 const int32_t* src, const int32_t* dst, void* stream) {
+    if (!rows_dev || frames < 1 || n < 1 || t < 1) return aur_fail(ctx, AUR_ERR_ARG, "aur_tome_map_rows: bad shape (frames %d, n %d, t %d)", frames, n, t);
+    if (t > 8192) return aur_fail(ctx, AUR_ERR_ARG, "aur_tome_map_rows: t = %d exceeds 8192 (a workgroup holds one frame's row table in LDS)", t);
+    if (r < 0 || r > (t - 1) / 2) return aur_fail(ctx, AUR_ERR_ARG, "aur_tome_map_rows: r = %d outside [0, (t - 1) / 2 = %d]", r, (t - 1) / 2);
+    if (r == 0) return AUR_OK;
+    if (!unm || !src || !dst) return aur_fail(ctx, AUR_ERR_ARG, "aur_tome_map_rows: unm / src / dst missing");
+    CK(launch_tome_map(rows_dev, frames, n, t, r, unm, src, dst, (hipStream_t)stream));
+    return AUR_OK;
+}
+
+extern "C" int aur_unmerge_rows(aur_ctx* ctx, const void* tokens, const int32_t* map, int32_t frames, int32_t n, int32_t n_kept, int32_t d,
+                                void* out, void* stream) {
+    if (!tokens || !map || !out || frames < 1 || n < 1 || n_kept < 1 || d < 8)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_unmerge_rows: bad shape (frames %d, n %d, n_kept %d, d %d)", frames, n, n_kept, d);
+    if (d & 7) return aur_fail(ctx, AUR_ERR_ARG, "aur_unmerge_rows: d = %d is not a multiple of 8 (rows move as 16-byte pieces)", d);
+    if (((uintptr_t)tokens | (uintptr_t)out) & 15) return aur_fail(ctx, AUR_ERR_ARG, "aur_unmerge_rows: tokens and out must be 16-byte aligned");
+    if (((int64_t)frames * n * (d >> 3) + 255) / 256 > 0x7fffffffll) return aur_fail(ctx, AUR_ERR_ARG, "aur_unmerge_rows: too many rows for one launch");
+    CK(launch_unmerge_rows((const half_t*)tokens, map, frames, n, n_kept, d, (half_t*)out, (hipStream_t)stream));
     return AUR_OK;
 }
 

@@ -116,6 +116,13 @@ hipError_t launch_tome_step(const TomeArgs& a, hipStream_t s);
 int64_t tome_mfrag_floats(int t, int c);          // floats of TomeArgs.mhat per frame
 // metric[f][tok][d] = mean over heads of K (read back from PAIRED K fragments of the ViT "pages")
 hipError_t launch_tome_metric(const KvLayout& kv, int frames, int t, int hd, float* metric, hipStream_t s);
+// the merge map (aurora_amd/merge_map.py): rows [frames][n] rewritten in place through one step's row table (r clamped, > 0; t <= 8192)
+hipError_t launch_tome_map(int32_t* rows, int frames, int n, int t, int r, const int32_t* unm, const int32_t* src, const int32_t* dst,
+                           hipStream_t s);
+hipError_t launch_tome_map_init(int32_t* map, int frames, int n, hipStream_t s);                     // map[f][p] = 1 + p
+// map -= 1; size_out [frames][n_kept] (may be null) = size[f][1 + k] of the padded size vector, ones when size is null
+hipError_t launch_tome_map_finish(int32_t* map, int frames, int n, const float* size, int t_pad, int n_kept, float* size_out, hipStream_t s);
+hipError_t launch_unmerge_rows(const half_t* tokens, const int32_t* map, int frames, int n, int n_kept, int d, half_t* out, hipStream_t s);
 
 // ---- vit.hip
 hipError_t launch_im2col(const half_t* pixels, int frames, int chans, int height, int width, int patch, int kpad, half_t* out,

@@ -520,3 +520,92 @@ hipError_t launch_tome_step(const TomeArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------ merge map: which input rows each output row stands for
+// (aurora_amd/merge_map.py is the definition; the reference's merge_source, tome.py:222-232, reduced to one int per input row.)
+// A step over t rows sends old row j to new row tab[j]: odd rows 2 i + 1 (B tokens) to nu + i, even rows 2 unm[k] to k, even rows
+// 2 src[k] to nu + dst[k] (nu = ceil(t / 2) - r: the merge kernel's output order above).  One workgroup per frame builds tab in LDS
+// (t <= 8192: 32 KiB of int32) from the index arrays the select launch wrote, then rewrites the frame's n entries in place through it.
+// Integer work only; its own launch BEHIND the step, on the step's stream, before the next layer reuses unm / src / dst.
+// Nothing the host has checked bounds the VALUES: every index is clamped into its range before it addresses LDS, and every entry into
+// [0, t) before the lookup, so whatever the buffers hold the kernel reads and writes its table and its n entries only.  Even rows no
+// index names (possible on caller data only) map to row 0.
+__global__ __launch_bounds__(256) void tome_map_kernel(int32_t* __restrict__ rows, int n, int t, int r, const int32_t* __restrict__ unm,
+                                                       const int32_t* __restrict__ src, const int32_t* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) int32_t mtab[];       // [t]
+    const int tid = threadIdx.x, f = blockIdx.x;
+    const int ta = (t + 1) >> 1, tb = t >> 1, nu = ta - r;
+    for (int j = tid; j < t; j += 256) mtab[j] = (j & 1) ? nu + (j >> 1) : 0;
+    __syncthreads();
+    for (int k = tid; k < nu; k += 256) {
+        const int a = min(max(unm[(int64_t)f * nu + k], 0), ta - 1);
+        mtab[2 * a] = k;
+    }
+    for (int k = tid; k < r; k += 256) {
+        const int a = min(max(src[(int64_t)f * r + k], 0), ta - 1);
+        const int b = min(max(dst[(int64_t)f * r + k], 0), tb - 1);
+        mtab[2 * a] = nu + b;
+    }
+    __syncthreads();
+    int32_t* row = rows + (int64_t)f * n;
+    for (int p = tid; p < n; p += 256) row[p] = mtab[min(max(row[p], 0), t - 1)];
+}
+
+// map[f][p] = 1 + p: the chain's start without the class row (row 0 never moves, merge_map.py)
+__global__ void tome_map_init_kernel(int32_t* __restrict__ map, int n, int64_t total) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id < total) map[id] = 1 + (int32_t)(id % n);
+}
+
+// the chain's end: the class row leaves both sides - map[f][p] -= 1, size_out[f][k] = size[f][1 + k] (ones where no layer merged)
+__global__ void tome_map_finish_kernel(int32_t* __restrict__ map, int frames, int n, const float* __restrict__ size, int t_pad, int n_kept,
+                                       float* __restrict__ size_out) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (map && id < (int64_t)frames * n) map[id] -= 1;
+    if (size_out && id < (int64_t)frames * n_kept) {
+        const int f = (int)(id / n_kept), k = (int)(id % n_kept);
+        size_out[id] = size ? size[(int64_t)f * t_pad + 1 + k] : 1.0f;
+    }
+}
+
+// out[f][p][:] = tokens[f][map[f][p]][:] - the reference's unmerge closures (tome.py:83-98) applied last layer first, as ONE gather.
+// One thread per 16-byte piece (d % 8 == 0); map entries clamped into [0, n_kept): a pure copy that cannot leave `tokens`.
+__global__ __launch_bounds__(256) void unmerge_rows_kernel(const half_t* __restrict__ tokens, const int32_t* __restrict__ map, int frames, int n,
+                                                           int n_kept, int d, half_t* __restrict__ out) {
+    const int pieces = d >> 3;
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (int64_t)frames * n * pieces) return;
+    const int pc = (int)(id % pieces);
+    const int64_t fp = id / pieces;                      // f * n + p
+    const int f = (int)(fp / n);
+    const int k = min(max(map[fp], 0), n_kept - 1);
+    *(h8*)(out + fp * d + pc * 8) = *(const h8*)(tokens + ((int64_t)f * n_kept + k) * d + pc * 8);
+}
+
+hipError_t launch_tome_map(int32_t* rows, int frames, int n, int t, int r, const int32_t* unm, const int32_t* src, const int32_t* dst,
+                           hipStream_t s) {
+    if (frames < 1 || n < 1 || t < 2 || t > 8192 || r < 1 || r > (t - 1) / 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tome_map_kernel, dim3(frames), dim3(256), (size_t)t * 4, s, rows, n, t, r, unm, src, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_tome_map_init(int32_t* map, int frames, int n, hipStream_t s) {
+    const int64_t total = (int64_t)frames * n;
+    hipLaunchKernelGGL(tome_map_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, map, n, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_tome_map_finish(int32_t* map, int frames, int n, const float* size, int t_pad, int n_kept, float* size_out, hipStream_t s) {
+    const int64_t total = (int64_t)frames * (n > n_kept ? n : n_kept);
+    hipLaunchKernelGGL(tome_map_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, map, frames, n, size, t_pad, n_kept,
+                       size_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_unmerge_rows(const half_t* tokens, const int32_t* map, int frames, int n, int n_kept, int d, half_t* out, hipStream_t s) {
+    if (frames < 1 || n < 1 || n_kept < 1 || d < 8 || (d & 7)) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)frames * n * (d >> 3);
+    if ((total + 255) / 256 > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(unmerge_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tokens, map, frames, n, n_kept, d, out);
+    return hipGetLastError();
+}

@@ -565,9 +565,11 @@ class AuroraCapEngine:
         return tome_r(height or v["image_size"], width or v["image_size"], v["patch_size"], token_kept_ratio,
                       v["num_hidden_layers"])
 
-    def vit_encode(self, pixels: torch.Tensor, r: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def vit_encode(self, pixels: torch.Tensor, r: int, out: Optional[torch.Tensor] = None, merge_map: bool = False):
         """pixels [F, C, H, W] -> hidden_states[-2][:, 1:]  as fp16 [F, n_kept, D] (into `out` when given: a captured front
-        end must not allocate)."""
+        end must not allocate).  merge_map=True: (tokens, map int32 [F, gh, gw], sizes fp32 [F, n_kept]) - map[f, y, x] is the row of
+        tokens[f] that patch (y, x) was merged into, sizes[f, k] the number of patches in row k (`aurora_amd.merge_map`); the
+        tokens are bitwise those of the plain call; `out` is then the three tensors, (tokens, map, sizes)."""
         v = self.v
         if pixels.dim() != 4 or pixels.shape[1] != v.get("num_channels", 3):
             raise ValueError(f"pixel_values must be [frames, {v.get('num_channels', 3)}, H, W], got {tuple(pixels.shape)}")
@@ -578,12 +580,27 @@ class AuroraCapEngine:
             raise ValueError(f"a {H}x{W} input has {t0} tokens per frame; this engine holds up to "
                              f"{(self.max_image // v['patch_size']) ** 2 + 1} (max_image {self.max_image})")
         n_kept = tokens_at_layer(t0, r, v["num_hidden_layers"] - 1) - 1
+        mp = sz = None
+        if merge_map and out is not None:                   # a captured call brings all three: (tokens, map, sizes)
+            out, mp, sz = out
+            grid = (F, H // v["patch_size"], W // v["patch_size"])
+            assert mp.shape == grid and mp.dtype == torch.int32 and mp.is_contiguous() and mp.is_cuda
+            assert sz.shape == (F, n_kept) and sz.dtype == torch.float32 and sz.is_contiguous() and sz.is_cuda
         if out is None:
             out = torch.empty(F, n_kept, v["hidden_size"], dtype=torch.float16, device=self.dev)
         else:
             assert out.shape == (F, n_kept, v["hidden_size"]) and out.dtype == torch.float16 and out.is_contiguous() and out.is_cuda
         nk = C.c_int32(0)
         pos = self.interpolated_pos(H, W)
+        if merge_map:
+            if mp is None:
+                mp = torch.empty(F, H // v["patch_size"], W // v["patch_size"], dtype=torch.int32, device=self.dev)
+                sz = torch.empty(F, n_kept, dtype=torch.float32, device=self.dev)
+            check(self.ctx, self.L.aur_vit_encode_map(self.ctx, px.data_ptr(), F, H, W, pos.data_ptr() if pos is not None else None, r,
+                                                      out.data_ptr(), mp.data_ptr(), sz.data_ptr(), C.byref(nk), self._stream()),
+                  "aur_vit_encode_map")
+            assert nk.value == n_kept
+            return out, mp, sz
         check(self.ctx, self.L.aur_vit_encode_hw(self.ctx, px.data_ptr(), F, H, W, pos.data_ptr() if pos is not None else None, r,
                                                  out.data_ptr(), C.byref(nk), self._stream()), "aur_vit_encode")
         assert nk.value == n_kept
@@ -1782,6 +1799,51 @@ class AuroraCapEngine:
                                              sr.data_ptr(), ds.data_ptr(), self._stream()), "aur_tome_step")
         torch.cuda.synchronize()
         return xo, so, dict(r=rl, node_idx=ni, unm_idx=un[:, : ta - rl], src_idx=sr[:, :rl], dst_idx=ds[:, :rl])
+
+    def tome_map_rows(self, rows: torch.Tensor, t: int, r: int, unm: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+        """One step of the merge map on caller data, in place (`merge_map.step_rows`; aur_tome_map_rows): rows int32 [F, n] on the
+        device, every entry the row of a step over `t` rows; unm [F, ceil(t/2) - r], src / dst [F, r] as `tome_step` returns them;
+        r already clamped to (t - 1) // 2.  Returns `rows`."""
+        if not (torch.is_tensor(rows) and rows.dim() == 2 and rows.dtype == torch.int32 and rows.is_contiguous() and rows.is_cuda):
+            raise ValueError("rows must be a contiguous int32 [frames, n] tensor on the device (it is rewritten in place)")
+        F, n = rows.shape
+        t, r = int(t), int(r)
+        if F < 1 or n < 1 or t < 1 or t > 8192:
+            raise ValueError(f"frames {F}, n {n}, t {t}: all >= 1 and t <= 8192")
+        if r < 0 or r > (t - 1) // 2:
+            raise ValueError(f"r = {r} outside [0, (t - 1) // 2 = {(t - 1) // 2}]")
+        idx = []
+        for name, a, w in (("unm", unm, (t + 1) // 2 - r), ("src", src, r), ("dst", dst, r)):
+            if r == 0:
+                idx.append(None)
+                continue
+            if not torch.is_tensor(a) or a.numel() != F * w:
+                raise ValueError(f"{name} must hold [frames, {w}] = {F * w} indices")
+            idx.append(a.to(device=self.dev, dtype=torch.int32).contiguous())
+        ptr = [a.data_ptr() if a is not None else None for a in idx]
+        check(self.ctx, self.L.aur_tome_map_rows(self.ctx, rows.data_ptr(), F, n, t, r, ptr[0], ptr[1], ptr[2], self._stream()),
+              "aur_tome_map_rows")
+        return rows
+
+    def unmerge(self, tokens: torch.Tensor, map: torch.Tensor) -> torch.Tensor:
+        """tokens [F, n_kept, d], map int [F, ...] -> fp16 [F, ..., d]: every patch gets the row of the token it was merged into
+        (`merge_map.unmerge`; aur_unmerge_rows).  d a multiple of 8."""
+        if not torch.is_tensor(tokens) or tokens.dim() != 3:
+            raise ValueError("tokens must be [frames, n_kept, d]")
+        if not torch.is_tensor(map) or map.dim() < 2 or map.shape[0] != tokens.shape[0] or map.is_floating_point():
+            raise ValueError(f"map must be an integer [frames = {tokens.shape[0]}, ...] tensor")
+        F, n_kept, d = tokens.shape
+        if d % 8:
+            raise ValueError(f"d = {d} is not a multiple of 8")
+        n = map[0].numel()
+        if F < 1 or n < 1 or n_kept < 1:
+            raise ValueError("empty tokens or map")
+        tk = self._h(tokens)
+        mp = map.to(device=self.dev, dtype=torch.int32).contiguous()
+        out = torch.empty(*map.shape, d, dtype=torch.float16, device=self.dev)
+        check(self.ctx, self.L.aur_unmerge_rows(self.ctx, tk.data_ptr(), mp.data_ptr(), F, n, n_kept, d, out.data_ptr(), self._stream()),
+              "aur_unmerge_rows")
+        return out
 
     def linear(self, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = 0,
                resid: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -84,9 +84,11 @@ class AuroraEncoder:
     def reset_tome_r(self, visual_token_merge_ratio: float):            # aurora.py:880-881
         self.visual_token_merge_ratio = visual_token_merge_ratio
 
-    def __call__(self, pixel_values: torch.Tensor) -> torch.Tensor:
+    def __call__(self, pixel_values: torch.Tensor, output_merge_map: bool = False):
+        """tokens [F, n_kept, D]; output_merge_map=True: (tokens, map int32 [F, gh, gw], sizes fp32 [F, n_kept]) - which token
+        every patch was merged into and how many patches each token holds (`aurora_amd.merge_map`)."""
         r = self._e.tome_r(self.visual_token_merge_ratio, pixel_values.shape[-2], pixel_values.shape[-1])
-        return self._e.vit_encode(pixel_values, r)
+        return self._e.vit_encode(pixel_values, r, merge_map=output_merge_map)
 
 
 class GenerateOutput:
@@ -133,8 +135,11 @@ class _LLM:
                  past_key_values=None, labels=None, eos_token_id="default", top_k="default", seed: int = 0, stream: int = 0,
                  output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                 min_new_tokens: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_ids=None, **unused):
-        """do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
+                 min_new_tokens: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_ids=None, merge_map=None,
+                 merge_sizes=None, **unused):
+        """`merge_map` / `merge_sizes` (what `AuroraModel.forward` adds with data["output_merge_map"]) are accepted and ignored, so
+        `generate(**out, ...)` keeps working.
+        do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
         sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
         passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
         ids are a function of (seed, stream) and the prompt alone.
@@ -325,16 +330,28 @@ class AuroraModel:
             raise ValueError(f"pixel_values must be [1, f, c, h, w] or [1, c, h, w], got {tuple(data['pixel_values'].shape)}")
         ids = data["input_ids"]
         ids = ids[0].tolist() if torch.is_tensor(ids) else list(ids[0])
+        want_map = bool(data.get("output_merge_map"))
+        maps = None
+        enc = (lambda p: self.visual_encoder(p, output_merge_map=True)) if want_map else self.visual_encoder
         if self.slowfast and px.shape[1] != 1:                                    # aurora.py:223-246
-            low = self.visual_encoder(px[0, 1:])                                  # frames 1.. at the current ratio
+            low = enc(px[0, 1:])                                                  # frames 1.. at the current ratio
             self.visual_encoder.visual_token_merge_ratio = 1.0                    # :231 - the reference leaves it at 1.0 too
-            high = self.visual_encoder(px[0, :1])                                 # frame 0 unmerged
+            high = enc(px[0, :1])                                                 # frame 0 unmerged
+            if want_map:                                                          # frame 0 carries the identity map and ones
+                (low, lmap, lsz), (high, hmap, hsz) = low, high
+                maps = (torch.cat([hmap, lmap], 0), [hsz[0]] + list(lsz))
             flat = torch.cat([high.reshape(-1, high.shape[-1]), low.reshape(-1, low.shape[-1])], 0)
             counts = [high.shape[1]] + [low.shape[1]] * low.shape[0]
             plan = self.engine.splice_plan(ids, px.shape[1], counts, strict=True)  # utils.py:297-431: marker i <- frame i
             embeds, L = self.engine.project_splice(flat, plan=plan)
         else:
-            vis = self.visual_encoder(px[0])                                      # aurora.py:249-253
+            vis = enc(px[0])                                                      # aurora.py:249-253
+            if want_map:
+                vis, vmap, vsz = vis
+                maps = (vmap, list(vsz))
             embeds, L = self.engine.project_splice(vis, ids)                     # aurora.py:254-258
-        return {"input_ids": None, "position_ids": None, "attention_mask": None, "past_key_values": None,
-                "inputs_embeds": embeds[:L].unsqueeze(0), "labels": None}         # utils.py:288-295
+        out = {"input_ids": None, "position_ids": None, "attention_mask": None, "past_key_values": None,
+               "inputs_embeds": embeds[:L].unsqueeze(0), "labels": None}          # utils.py:288-295
+        if want_map:                      # merge_map int32 [f, gh, gw], merge_sizes: f tensors fp32 [tokens of that frame] (merge_map.py)
+            out["merge_map"], out["merge_sizes"] = maps
+        return out

@@ -117,6 +117,20 @@ int aur_vit_pos_interp(aur_ctx* ctx, int32_t height, int32_t width, void* pos_ou
 
 int aur_vit_encode_hw(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t height, int32_t width,
                       const void* pos_emb, int32_t r, void* out_tokens, int32_t* n_kept_out, void* stream);
+/* aur_vit_encode_hw with the merge map (aurora_amd/merge_map.py; the reference's merge_source, tome.py:222-232, carried through every
+ * layer): which kept token every patch was merged into.  Two more outputs in device memory:
+ *   map_out  int32 [frames, (height / patch) * (width / patch)], patches row-major: map_out[f][p] in [0, n_kept) is the row of
+ *            out_tokens' frame f that patch p ended in;
+ *   size_out fp32 [frames, n_kept] or NULL: patches per kept token - the size vector of merge_wavg (tome.py:207-219) without its class
+ *            entry; bincount(map_out[f]) == size_out[f], exactly.
+ * The map is built in map_out itself - set to 1 + p, rewritten through the layer's row table by one launch of its own behind the ToMe
+ * step of every merging layer (on the same stream, before the next layer reuses the step's index buffers), the class row taken off at
+ * the end - so aur_workspace_bytes does not grow, nothing is allocated, and the call is enqueue-only and recordable with
+ * aur_graph_begin like aur_vit_encode_hw.  r = 0, or a schedule that never merges: the identity and ones.  out_tokens are bitwise those of
+ * aur_vit_encode_hw, which IS this call with map_out = size_out = NULL and launches exactly the kernels it launched before. */
+int aur_vit_encode_map(aur_ctx* ctx, const void* pixels, int32_t frames, int32_t height, int32_t width,
+                       const void* pos_emb, int32_t r, void* out_tokens, int32_t* map_out, float* size_out,
+                       int32_t* n_kept_out, void* stream);
 
 /* projector + prefix splice: replaces self.projector(...) (aurora.py:254-256) and
  * prepare_inputs_labels_for_multimodal (model/utils.py:138-295) for one sequence.
@@ -327,6 +341,22 @@ int aur_decode_stamps_read(aur_ctx* ctx, double* us_out, int32_t cap, int64_t* s
 int aur_tome_step(aur_ctx* ctx, const float* metric, const void* x, const float* size, int32_t frames,
                   int32_t t, int32_t c, int32_t d, int32_t r, void* x_out, float* size_out,
                   int32_t* node_idx, int32_t* unm_idx, int32_t* src_idx, int32_t* dst_idx, void* stream);
+
+/* The merge-map step alone on caller data (tome.hip tome_map_kernel; aurora_amd/merge_map.py step_rows): rows_dev int32 [frames, n], in
+ * and out, entry e of frame f becomes the new row of old row e under ONE ToMe step over t rows - odd rows 2 i + 1 go to
+ * ceil(t / 2) - r + i, even rows 2 unm[k] to k, even rows 2 src[k] to ceil(t / 2) - r + dst[k].  unm [frames, ceil(t / 2) - r], src and dst
+ * [frames, r]: device int32, the shapes aur_tome_step returns.  0 <= r <= (t - 1) / 2 (the caller clamps); r = 0 is a no-op.  t <= 8192,
+ * the limit of aur_tome_step (a workgroup holds one frame's row table in LDS).  Anything else returns AUR_ERR_ARG and leaves the ctx
+ * usable.  The host never sees the values: entries are clamped into [0, t) and indices into their ranges before they address anything.
+ * Enqueue-only. */
+int aur_tome_map_rows(aur_ctx* ctx, int32_t* rows_dev, int32_t frames, int32_t n, int32_t t, int32_t r, const int32_t* unm,
+                      const int32_t* src, const int32_t* dst, void* stream);
+/* out[f][p][:] = tokens[f][map[f][p]][:]: the reference's unmerge closures (tome.py:83-98) applied from the last layer back to the first,
+ * as one gather.  tokens fp16 [frames, n_kept, d]; map device int32 [frames, n], entries clamped into [0, n_kept); out fp16
+ * [frames, n, d].  A pure copy in 16-byte pieces: a d that is not a multiple of 8, or a tokens / out that is not 16-byte aligned, returns
+ * AUR_ERR_ARG.  Enqueue-only. */
+int aur_unmerge_rows(aur_ctx* ctx, const void* tokens, const int32_t* map, int32_t frames, int32_t n, int32_t n_kept, int32_t d,
+                     void* out, void* stream);
 
 /* C[M, n] = act(A[M, K] W^T + bias) (+ resid): replaces F.linear.  w_packed from aur_pack_linear
  * (npad % 128 == 0, K % 64 == 0, K >= 64, n % 4 == 0, 4 <= n <= npad: the rules of aur_gemm_rows at lda = K, ldc = ldr = n); bias fp32

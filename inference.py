@@ -61,7 +61,37 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--logprobs', type=int, default=None, metavar='N',
                         help='after the caption: one line per generated token - id, decoded piece, log-probability under the model\'s '
                              'unmodified distribution, and its N (0 .. 8) most likely alternatives -, then their sum and exp(-mean)')
+    # which patches each visual token stands for (aurora_amd.merge_map); neither flag changes the caption line
+    parser.add_argument('--merge_map', default=None, metavar='OUT.npz',
+                        help='write the merge map of the visual tokens: merge_map int32 [frames, gh, gw] (the kept token every patch was merged '
+                             'into), sizes (patches per kept token, one row per frame), grid and token_kept_ratio')
+    parser.add_argument('--merge_vis', default=None, metavar='OUT.png',
+                        help='write the frames side by side with every patch filled with the mean colour of its merged group and a line '
+                             'between neighbouring patches of different groups')
     return parser
+
+
+def write_merge_outputs(args, output, pixel_values, patch):
+    """--merge_map / --merge_vis: the map `model(data)` returned, as an npz and as a picture (`merge_map.render`; host work)."""
+    from aurora_amd import merge_map as MM
+    from aurora_amd.preprocess import CLIP_MEAN, CLIP_STD
+    mp = output["merge_map"].cpu().numpy()
+    szs = [s.cpu().numpy() for s in output["merge_sizes"]]
+    if args.merge_map:
+        width = max(len(s) for s in szs)
+        sizes = np.zeros((len(szs), width), np.float32)                # slow-fast frames keep different counts: rows padded with 0
+        for f, s in enumerate(szs):
+            sizes[f, :len(s)] = s
+        with open(args.merge_map, "wb") as fh:
+            np.savez(fh, merge_map=mp, sizes=sizes, n_kept=np.array([len(s) for s in szs], np.int32),
+                     grid=np.array(mp.shape[1:], np.int32), token_kept_ratio=np.float64(args.token_kept_ratio))
+    if args.merge_vis:
+        from PIL import Image
+        px = pixel_values[0] if pixel_values.dim() == 5 else pixel_values
+        px = px.float().cpu().numpy().transpose(0, 2, 3, 1)            # the normalised input frames back to 8-bit RGB
+        rgb = np.clip(np.rint((px * np.asarray(CLIP_STD, np.float32) + np.asarray(CLIP_MEAN, np.float32)) * 255.0), 0, 255).astype(np.uint8)
+        img = MM.render(rgb, mp, patch)
+        Image.fromarray(np.concatenate(list(img), axis=1)).save(args.merge_vis)
 
 
 def print_logprobs(out, tokenizer):
@@ -85,6 +115,9 @@ def main():
         sys.exit("error: --logprobs takes a number of alternatives in [0, 8]")
     if args.logprobs is not None and (args.extra_prompt or args.score is not None):
         sys.exit("error: --logprobs goes with one generated caption (not with --extra_prompt or --score)")
+    want_map = args.merge_map is not None or args.merge_vis is not None
+    if want_map and (args.extra_prompt or args.score is not None):
+        sys.exit("error: --merge_map / --merge_vis go with one generated caption (not with --extra_prompt or --score)")
     rule_args = {k: getattr(args, k) for k in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens") if getattr(args, k) is not None}
     try:
         from aurora_amd.logit_rules import check_logit_rules
@@ -190,7 +223,11 @@ def main():
         for ids in outs:
             print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
         return
+    if want_map:
+        data["output_merge_map"] = True
     output = model(data, mode="inference")
+    if want_map:
+        write_merge_outputs(args, output, data["pixel_values"], model.visual_encoder.config["patch_size"])
     sample = dict(top_k=args.top_k, seed=args.seed) if args.do_sample else {}
     cont = model.llm.generate(**output, do_sample=args.do_sample, temperature=args.temperature, top_p=args.top_p,
                               num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample, **rule_args,
