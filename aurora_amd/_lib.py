@@ -140,6 +140,12 @@ SIGNATURES = {
     "aur_get_logprobs": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "aur_slot_collect_logprobs": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "aur_token_logprob_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "aur_attn_map_bytes": (_L, [_P, _I]),
+    "aur_attn_map_enable": (C.c_int, [_P, _I, C.c_uint64, _P, _L, _P]),
+    "aur_get_attn_map": (C.c_int, [_P, _P, _P]),
+    "aur_slot_collect_attn_map": (C.c_int, [_P, _I, _I, _P, _P]),
+    "aur_attn_map_rows_scratch_bytes": (_L, [_P, _I, _I]),
+    "aur_attn_map_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _L, _I, _P, _P]),
     "aur_set_option": (C.c_int, [_P, C.c_char_p, _L]),
     "aur_microbench": (C.c_int, [_P, C.c_char_p, _I, C.POINTER(C.c_double), _P]),
     "aur_profile_enable": (C.c_int, [_P, _I]),

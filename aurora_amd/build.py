@@ -14,14 +14,16 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libaurora_hip.so")
-SOURCES = ["engine.hip", "gemm.hip", "gemm256.hip", "attn.hip", "norm.hip", "tome.hip", "vit.hip", "decode.hip", "sample.hip", "logit_rules.hip", "stop.hip", "score.hip", "preprocess.hip"]
+SOURCES = ["engine.hip", "gemm.hip", "gemm256.hip", "attn.hip", "norm.hip", "tome.hip", "vit.hip", "decode.hip", "sample.hip", "logit_rules.hip", "stop.hip", "score.hip", "attn_map.hip", "preprocess.hip"]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # tome.hip carries the bit-exact fp32 contract: no implicit FMA contraction
 # preprocess.hip computes Pillow's resampling taps in doubles on the host: same rule
 # logit_rules.hip is bitwise transformers' fp32 multiply / divide: same rule
 # attn.hip rescales its output accumulators every key block: keep them in VGPRs (MFMA VGPR form) instead of paying
 # 224 v_accvgpr_read/write per block for the AGPR round trip
+# attn_map.hip states which multiply-adds are fused (the pages' join) and which are not (the weight, then the add into the row): same rule
 PER_FILE = {"tome.hip": ["-ffp-contract=off"], "preprocess.hip": ["-ffp-contract=off"], "logit_rules.hip": ["-ffp-contract=off"],
+            "attn_map.hip": ["-ffp-contract=off"],
             "attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 

@@ -112,6 +112,11 @@ struct aur_ctx {
         int32_t *lp_len = nullptr, *lp_top_id = nullptr;
         float *lp = nullptr, *lp_top_lp = nullptr;
         int lp_top_n = 0;
+        // attention over the prompt during decode (aur_attn_map_enable): the caller's buffer, nullptr = off.  am [b][max_new][am_window]:
+        // rows max_new apart, like s_ids; am_score / am_ml: the recorder's scratch (attn_map.hip); am_mask bit l = layer l records
+        float *am = nullptr, *am_score = nullptr, *am_ml = nullptr;
+        int am_window = 0, am_nlayers = 0;
+        uint64_t am_mask = 0;
         int batch = 0, max_new = 0, eos = -1;
         hipGraphExec_t graph = nullptr, graph_h = nullptr;   // decode step: full grid / half grid (decode_half)
         int graph_batch = 0;
@@ -1113,9 +1118,29 @@ static SkinnyArgs mk_dec_down(aur_ctx* ctx, int l) {
                      ctx->l_dpad, ctx->cfg.llm_hidden);
 }
 
-// slots [b0, b0 + nb) of bank K hold no log-probability record: wherever their s_len is zeroed
-static int logprob_clear(aur_ctx* ctx, const aur_ctx::Bank& K, int b0, int nb, hipStream_t s) {
+// ---- attention over the prompt during decode: the recorder's launch for layer l of the decode step
+static bool attn_map_layer(const aur_ctx::Bank& K, int l) { return l < 64 && ((K.am_mask >> l) & 1); }
+static AttnMapArgs mk_attn_map(const aur_ctx* ctx, int l, const int32_t* pos, int B, int window, float* score, float* ml, float* out) {
+    AttnMapArgs a{};
+    a.qbuf = ctx->d_q; a.kv = llm_kv(ctx, l); a.pos = pos; a.B = B; a.heads = ctx->cfg.llm_heads; a.scale = 1.0f / sqrtf((float)ctx->l_hd);
+    a.window = window; a.score = score; a.page_ml = ml; a.s_len = nullptr; a.s_fin = nullptr; a.max_new = 1; a.out = out;
+    a.weight = 1.0f / (float)ctx->cfg.llm_heads; a.first = 1;
+    return a;
+}
+static AttnMapArgs mk_dec_attn_map(const aur_ctx* ctx, int l) {
+    const aur_ctx::Bank& K = ctx->bank();
+    AttnMapArgs a = mk_attn_map(ctx, l, K.s_pos, K.batch, K.am_window, K.am_score, K.am_ml, K.am);
+    a.s_len = K.s_len; a.s_fin = K.s_fin; a.max_new = K.max_new;
+    a.weight = 1.0f / (float)(ctx->cfg.llm_heads * K.am_nlayers);
+    a.first = (K.am_mask & ((1ull << l) - 1)) == 0;
+    return a;
+}
+
+// slots [b0, b0 + nb) of bank K hold no log-probability record and no attention record: wherever their s_len is zeroed
+static int slot_records_clear(aur_ctx* ctx, const aur_ctx::Bank& K, int b0, int nb, hipStream_t s) {
     if (K.lp_len) CK(launch_token_logprob_clear(b0, nb, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id, K.lp_top_lp, s));
+    // and no attention record (aur_attn_map_enable): their rows are zeros, a fill node like the s_len memsets beside every call of this
+    if (K.am) CK(hipMemsetAsync(K.am + (int64_t)b0 * K.max_new * K.am_window, 0, (size_t)nb * K.max_new * K.am_window * 4, s));
     return AUR_OK;
 }
 
@@ -1144,7 +1169,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
     CK(hipMemsetAsync(K.s_ssq_mlp, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
     CK(hipMemsetAsync(K.s_ssq_attn, 0, AUR_SSQ_SLOTS * AUR_MAX_BATCH * 8, s));
-    return logprob_clear(ctx, K, 0, g.max_batch, s);
+    return slot_records_clear(ctx, K, 0, g.max_batch, s);
 }
 
 // logits for batch columns [b0, b0 + nb) from the residual rows in d_x (x-fragment form; final RMSNorm folded into the
@@ -1403,7 +1428,7 @@ static int run_pass(aur_ctx* ctx, int kind, const PrefillPass& p, int slot0, hip
     CK(hipMemsetAsync(K.s_fin + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_pos + slot0, 0, (size_t)nseq * 4, s));
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot0 * K.max_new, 0, (size_t)nseq * K.max_new * 4, s));
-    if (int rc = logprob_clear(ctx, K, slot0, nseq, s)) return rc;
+    if (int rc = slot_records_clear(ctx, K, slot0, nseq, s)) return rc;
     return prefill_first_tokens(ctx, slot0, p, "prefill_commit", s);
 }
 // an entry point = its name, its tail, its form: slots [slot0 ..) for BATCH / COMMIT, KV sequences [seq0 ..) for the rows (BATCH: seq0 == slot0)
@@ -1642,6 +1667,46 @@ extern "C" int aur_attn_decode_rows(aur_ctx* ctx, const void* x, int32_t rows, i
     return AUR_OK;
 }
 
+// The attention-map kernels alone on caller rows, beside aur_attn_decode_rows: the same QKV launch writes the caller's q into d_q and
+// its k at pos_b into the pages, then the recorder runs for one layer and all heads.  Scratch: aur_attn_decode_rows' | scores | page sums.
+static int64_t attn_map_score_bytes(const aur_ctx* c, int window) { return rup64((int64_t)c->cfg.max_batch * c->cfg.llm_heads * window * 4, 256); }
+static int64_t attn_map_ml_bytes(const aur_ctx* c) { return rup64((int64_t)c->cfg.max_batch * c->cfg.llm_heads * c->l_max_pages * 2 * 4, 256); }
+static bool attn_map_window_ok(const aur_ctx* c, int window) {
+    return window >= 64 && window % 64 == 0 && window <= c->l_ctx_pad && c->cfg.llm_heads <= AUR_ATTN_MAP_MAX_HEADS;
+}
+extern "C" int64_t aur_attn_map_rows_scratch_bytes(const aur_ctx* ctx, int32_t kx, int32_t window) {
+    if (!ctx || kx < 1 || !attn_map_window_ok(ctx, window)) return 0;
+    return aur_attn_decode_scratch_bytes(ctx, kx) + attn_map_score_bytes(ctx, window) + attn_map_ml_bytes(ctx);
+}
+extern "C" int aur_attn_map_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, const void* w_packed, int32_t npad, const int32_t* pos_dev,
+                                 int32_t rope, void* scratch, int64_t scratch_bytes, int32_t window, float* out, void* stream) {
+    const char* who = "aur_attn_map_rows";
+    if (!ctx || !x || !w_packed || !pos_dev || !out) return aur_fail(ctx, AUR_ERR_ARG, "%s: null argument", who);
+    if (!ctx->finalized || ctx->ll.empty() || !ctx->kvpool) return aur_fail(ctx, AUR_ERR_STATE, "%s: language weights not finalized", who);
+    const aur_config& g = ctx->cfg;
+    if (rows < 1 || rows > g.max_batch || kx < 128 || (kx & 127)) return aur_fail(ctx, AUR_ERR_ARG, "%s: need 1 <= rows <= max_batch %d and kx a positive multiple of 128 (got %d, %d)", who, g.max_batch, rows, kx);
+    if (npad != ctx->l_qkv_npad) return aur_fail(ctx, AUR_ERR_ARG, "%s: npad %d is not the language model's packed QKV width %d", who, npad, ctx->l_qkv_npad);
+    if (!attn_map_window_ok(ctx, window)) return aur_fail(ctx, AUR_ERR_ARG, "%s: window %d is not a multiple of 64 in [64, %d] (or more than %d heads)", who, window, ctx->l_ctx_pad, AUR_ATTN_MAP_MAX_HEADS);
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < aur_attn_map_rows_scratch_bytes(ctx, kx, window))
+        return aur_fail(ctx, AUR_ERR_ARG, "%s: scratch must be 256-byte aligned and hold aur_attn_map_rows_scratch_bytes = %lld bytes (got %lld)", who,
+                        (long long)aur_attn_map_rows_scratch_bytes(ctx, kx, window), (long long)scratch_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    half_t* xf = (half_t*)scratch;
+    float2* ident = (float2*)((char*)scratch + attn_dec_xf_bytes(ctx, kx));
+    float* score = (float*)((char*)scratch + aur_attn_decode_scratch_bytes(ctx, kx));
+    float* ml = (float*)((char*)score + attn_map_score_bytes(ctx, window));
+    CK(hipMemsetAsync(xf, 0, (size_t)rup(rows, 16) * kx * 2, s));
+    CK(launch_xfrag_pack((const half_t*)x, kx, rows, kx, xf, s));
+    if (!rope) {
+        const int n = ctx->l_ctx_pad * (ctx->l_hd / 2);
+        hipLaunchKernelGGL(rope_identity_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ident, n);
+        CK(hipGetLastError());
+    }
+    CK(launch_skinny(mk_sk_qkv(ctx, 0, xf, (const half_t*)w_packed, rows, kx, rope ? ctx->l_rope : ident, pos_dev, nullptr, nullptr), s));
+    CK(launch_attn_map(mk_attn_map(ctx, 0, pos_dev, rows, window, score, ml, out), s));
+    return AUR_OK;
+}
+
 // One decode projection alone on caller rows (parity tests): the production producer of x fragments (and sum(x^2)) at batch rows
 // [b0, b0 + rows), then launch_skinny with arguments from the builders the decode step itself uses (mk_sk_row / mk_sk_gateup / mk_lm_head):
 // the structure - variant, split-K partials, fused reduce, k phases of gate/up, half grid - is mk_skinny's, stated nowhere else.  Everything else is
@@ -1736,6 +1801,7 @@ static int enqueue_decode_step(aur_ctx* ctx, hipStream_t s, bool instrument) {
     const int B = ctx->bank().batch;
     for (int l = 0; l < g.llm_layers; ++l) {
         CK(launch_skinny(mk_dec_qkv(ctx, l), s));
+        if (ctx->bank().am && attn_map_layer(ctx->bank(), l)) CK(launch_attn_map(mk_dec_attn_map(ctx, l), s));       // the layer's roped q is in d_q, its newest key in the pages
         {
             const DecAttnArgs at = mk_dec_attn(ctx, l);
             const bool stamp = l == ctx->stamp_layer && ctx->d_stamp && !instrument;
@@ -1926,7 +1992,7 @@ extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
     CK(hipMemsetAsync(K.s_rules + slot, 0, sizeof(aur_logit_rules), s));
     if (K.s_stop) CK(hipMemsetAsync(K.s_stop + slot, 0, sizeof(aur_stop_rules), s));
-    return logprob_clear(ctx, K, slot, 1, s);
+    return slot_records_clear(ctx, K, slot, 1, s);
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
     if (int rc = slot_check(ctx, slot, "aur_slot_retire")) return rc;
@@ -2026,6 +2092,62 @@ extern "C" int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t
     if (top_n < 0 || top_n > 8 || (top_n && (!top_ids_out || !top_lp_out)))
         return aur_fail(ctx, AUR_ERR_ARG, "aur_token_logprob_rows: top_n %d outside [0, 8], or null outputs for it", top_n);
     CK(launch_token_logprob_rows(logits, rows, vocab, tokens_dev, top_n, lp_out, top_ids_out, top_lp_out, (hipStream_t)stream));
+    return AUR_OK;
+}
+// ---- attention over the prompt during decode.  Buffer: records fp32 [max_batch][max_new_tokens][window] | scores | page sums
+static int64_t attn_map_rec_bytes(const aur_ctx* c, int window) { return rup64((int64_t)c->cfg.max_batch * c->cfg.max_new_tokens * window * 4, 256); }
+extern "C" int64_t aur_attn_map_bytes(const aur_ctx* ctx, int32_t window) {
+    if (!ctx || !attn_map_window_ok(ctx, window)) return -1;
+    return attn_map_rec_bytes(ctx, window) + attn_map_score_bytes(ctx, window) + attn_map_ml_bytes(ctx);
+}
+extern "C" int aur_attn_map_enable(aur_ctx* ctx, int32_t window, uint64_t layer_mask, void* buf_dev, int64_t nbytes, void* stream) {
+    NO_CAPTURE("aur_attn_map_enable");
+    aur_ctx::Bank& K = ctx->bank();
+    const aur_config& g = ctx->cfg;
+    uint64_t mask = 0;
+    if (buf_dev) {
+        if (!attn_map_window_ok(ctx, window))
+            return aur_fail(ctx, AUR_ERR_ARG, "aur_attn_map_enable: window %d is not a multiple of 64 in [64, %d] (or more than %d heads)", window, ctx->l_ctx_pad, AUR_ATTN_MAP_MAX_HEADS);
+        const uint64_t all = g.llm_layers >= 64 ? ~0ull : ((1ull << g.llm_layers) - 1);
+        mask = layer_mask ? layer_mask : all;
+        if (g.llm_layers > 64 || (mask & ~all)) return aur_fail(ctx, AUR_ERR_ARG, "aur_attn_map_enable: layer mask 0x%llx names a layer outside [0, %d) (at most 64 layers)", (unsigned long long)layer_mask, g.llm_layers);
+        if (((uintptr_t)buf_dev & 255) || nbytes < aur_attn_map_bytes(ctx, window))
+            return aur_fail(ctx, AUR_ERR_ARG, "aur_attn_map_enable: buffer of %lld bytes (need %lld, 256-byte aligned)", (long long)nbytes, (long long)aur_attn_map_bytes(ctx, window));
+    }
+    // whether the step launches the recorder, for which layers and with which pointers, is frozen inside this bank's captured decode graphs
+    if (K.graph || K.graph_h) {
+        (void)hipDeviceSynchronize();
+        drop_graphs(K);
+    }
+    K.am = nullptr;
+    if (!buf_dev) return AUR_OK;
+    CK(hipMemsetAsync(buf_dev, 0, (size_t)attn_map_rec_bytes(ctx, window), (hipStream_t)stream));
+    K.am = (float*)buf_dev;
+    K.am_score = (float*)((char*)buf_dev + attn_map_rec_bytes(ctx, window));
+    K.am_ml = (float*)((char*)K.am_score + attn_map_score_bytes(ctx, window));
+    K.am_window = window; K.am_mask = mask; K.am_nlayers = __builtin_popcountll(mask);
+    return AUR_OK;
+}
+// counterpart of aur_get_logprobs: synchronises.  map_host fp32 [batch * max_new_tokens of the batch * window]
+extern "C" int aur_get_attn_map(aur_ctx* ctx, float* map_host, void* stream) {
+    NO_CAPTURE("aur_get_attn_map");
+    hipStream_t s = (hipStream_t)stream;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.am || K.batch < 1) return aur_fail(ctx, AUR_ERR_STATE, "aur_get_attn_map: not enabled on this bank (aur_attn_map_enable), or no active batch");
+    if (!map_host) return aur_fail(ctx, AUR_ERR_ARG, "aur_get_attn_map: null output");
+    CK(hipMemcpyAsync(map_host, K.am, (size_t)K.batch * K.max_new * K.am_window * 4, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    return AUR_OK;
+}
+// counterpart of aur_slot_collect_logprobs: device-to-device, enqueue-only, recordable.  out_dev fp32 [nslots][max_new_tokens of the batch][window]
+extern "C" int aur_slot_collect_attn_map(aur_ctx* ctx, int32_t slot0, int32_t nslots, float* out_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_collect_attn_map")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.am) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_collect_attn_map: not enabled on this bank (aur_attn_map_enable)");
+    if (nslots < 1 || slot0 + nslots > K.batch || !out_dev)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_collect_attn_map: slots [%d, %d) outside the batch of %d, or a null output", slot0, slot0 + nslots, K.batch);
+    const int64_t per = (int64_t)K.max_new * K.am_window;
+    CK(hipMemcpyAsync(out_dev, K.am + slot0 * per, (size_t)nslots * per * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return AUR_OK;
 }
 extern "C" int aur_slot_sampling(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_sampling* params_dev, void* stream) {

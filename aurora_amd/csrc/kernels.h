@@ -207,6 +207,25 @@ hipError_t launch_decode_attention(const DecAttnArgs& a, hipStream_t s);        
 hipError_t launch_decode_attention_main(const DecAttnArgs& a, hipStream_t s);
 hipError_t launch_decode_attention_combine(const DecAttnArgs& a, hipStream_t s);
 
+// ---- attn_map.hip: the decode step's attention over a prefix window of the keys, mean over heads (and over the layers that launch it)
+#define AUR_ATTN_MAP_MAX_HEADS 128
+struct AttnMapArgs {
+    const half_t* qbuf;     // [B][heads][kblk][4][8]: the roped queries the step's QKV projection wrote
+    KvLayout kv;
+    const int32_t* pos;     // [B]: keys valid = pos[b] + 1
+    int B, heads;
+    float scale;
+    int window;             // W: keys [0, W) are recorded, a multiple of 64
+    float* score;           // scratch [B][heads][W]: scale log2(e) q . k_j
+    float* page_ml;         // scratch [B][heads][kv.max_pages][2]: (max, sum of exp2(score - max)) of every 64-token page
+    const int32_t *s_len, *s_fin;     // decode step: slot b writes row s_len[b] unless finished / s_len outside [1, max_new); nullptr: every row b writes row 0
+    int max_new;            // rows per slot of `out` (1 with s_len == nullptr)
+    float* out;             // [B][max_new][W]
+    float weight;           // 1 / (heads x selected layers)
+    int first;              // 1: the first selected layer stores the row; 0: adds to it
+};
+hipError_t launch_attn_map(const AttnMapArgs& a, hipStream_t s);
+
 hipError_t launch_argmax_advance(const float* logits, int b0, int nb, int vocab, const half_t* embed, int d, int eos_id,
                                  int max_new, int32_t* out_ids, int32_t* out_len, int32_t* finished, int32_t* pos,
                                  half_t* xf, unsigned long long* ssq, int advance_pos, int set_pos, hipStream_t s,

@@ -21,6 +21,7 @@ from . import logit_rules as LR
 from . import stopping as ST
 from . import sampling as S
 from .scoring import check_logprobs
+from . import attn_map as AM
 from ._lib import AurConfig, check
 
 IMAGE_TOKEN_INDEX = -200     # src/xtuner/xtuner/utils/constants.py:4
@@ -345,6 +346,8 @@ class AuroraCapEngine:
         self._stop_table_dev = None                      # ... and on the device (caller-owned memory of aur_stop_vocab)
         self._lp_bufs: Dict[int, torch.Tensor] = {}      # bank -> the caller-owned state of aur_logprob_enable (kept once allocated)
         self._lp_top: Dict[int, int] = {}                # bank -> top_n it records with; absent = off
+        self._am_bufs: Dict[int, torch.Tensor] = {}      # bank -> the caller-owned state of aur_attn_map_enable (kept once allocated)
+        self._am_on: Dict[int, tuple] = {}               # bank -> (window, layers or None) it records with; absent = off
         self.c = c
         self.v, self.l = v, l
         self.max_new_tokens = max_new_tokens
@@ -995,6 +998,95 @@ class AuroraCapEngine:
         torch.cuda.synchronize()
         return lp.cpu().numpy(), tid.cpu().numpy()[:, :top_n], tlp.cpu().numpy()[:, :top_n]
 
+    # ------------------------------------------------------------------ attention over the prompt during decode
+    def _attn_map_on(self, window: int, layers=None):
+        """The current bank records, for every token it generates from now on, the attention of its decode step over keys
+        [0, window) - mean over `layers` (None = all) and all heads, as `aurora_amd.attn_map` defines it: two more launches behind the
+        QKV projection of every selected layer.  The state is a buffer this engine allocates per bank on first use; the bank's decode
+        graphs are re-captured once and the front-end graphs dropped when the choice changes (they hold slot resets and commits, which
+        clear the rows).  Sticky, like `_logprobs_on` (`attn_map_off` ends it).  A process that never asks never gets here."""
+        want = (int(window), None if layers is None else tuple(layers))
+        if self._am_on.get(self._bank) == want:
+            return
+        nbytes = int(self.L.aur_attn_map_bytes(self.ctx, want[0]))
+        if nbytes < 0:
+            raise ValueError(f"attn_map keys={want[0]} is not a multiple of 64 within the engine's context of {self.c.max_ctx}")
+        self._drop_front_graphs()
+        buf = self._am_bufs.get(self._bank)
+        if buf is None or buf.numel() < nbytes:
+            torch.cuda.synchronize(self.dev)                      # queued steps may still write the buffer this one replaces
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        check(self.ctx, self.L.aur_attn_map_enable(self.ctx, want[0], AM.layer_mask(want[1]), buf.data_ptr(), buf.numel(), self._stream()),
+              "aur_attn_map_enable")
+        self._am_bufs[self._bank], self._am_on[self._bank] = buf, want
+
+    def attn_map_off(self):
+        """No bank records attention any more: the launches are those of an engine that never asked (the buffers are kept for the
+        next request)."""
+        if not self._am_on:
+            return
+        self._drop_front_graphs()
+        bank = self._bank
+        for b in sorted(self._am_on):
+            self.select_bank(b)
+            check(self.ctx, self.L.aur_attn_map_enable(self.ctx, 0, 0, None, 0, self._stream()), "aur_attn_map_enable")
+            del self._am_on[b]
+        self.select_bank(bank)
+
+    def attn_map_state(self) -> np.ndarray:
+        """The current bank's records as numpy (synchronises): float32 [batch, max_new, window].  Row 0 of a slot and rows at or beyond
+        its length are zeros."""
+        W = self._am_on[self._bank][0]
+        out = np.zeros((self._batch, self._max_new, W), np.float32)
+        check(self.ctx, self.L.aur_get_attn_map(self.ctx, out.ctypes.data_as(C.c_void_p), self._stream()), "aur_get_attn_map")
+        return out
+
+    def slot_collect_attn_map(self, slot0: int, nslots: int, out_dev: torch.Tensor):
+        """Async device copy of the records of slots [slot0, slot0 + nslots) (`slot_collect`'s counterpart): out_dev float32
+        [nslots, max_new, window of the bank]."""
+        W = self._am_on[self._bank][0]
+        assert out_dev.dtype == torch.float32 and out_dev.is_cuda and out_dev.is_contiguous() and out_dev.numel() >= nslots * self._max_new * W
+        check(self.ctx, self.L.aur_slot_collect_attn_map(self.ctx, slot0, nslots, out_dev.data_ptr(), self._stream()), "aur_slot_collect_attn_map")
+
+    def attn_map_rows(self, x: torch.Tensor, w_packed: torch.Tensor, pos, window: int, *, rope: bool = False) -> torch.Tensor:
+        """The recorder's kernels alone (aur_attn_map_rows), beside `attn_decode_rows` and with its arguments: one decode step's QKV
+        write on caller rows x [B, kx], then the attention of row b over keys [0, window) of KV sequence b at position pos[b] - one
+        layer, mean over all heads.  Returns float32 [B, window] on the device."""
+        xh = self._h(x)
+        B, kx = xh.shape
+        pos_t = self._i32_arg(pos, B, "pos")
+        scratch = torch.empty(max(int(self.L.aur_attn_map_rows_scratch_bytes(self.ctx, kx, int(window))), 256), dtype=torch.uint8, device=self.dev)
+        out = torch.full((B, int(window)), float("nan"), dtype=torch.float32, device=self.dev)
+        check(self.ctx, self.L.aur_attn_map_rows(self.ctx, xh.data_ptr(), B, kx, w_packed.data_ptr(), w_packed.numel() // kx, pos_t.data_ptr(),
+                                                 int(rope), scratch.data_ptr(), scratch.numel(), int(window), out.data_ptr(), self._stream()),
+              "aur_attn_map_rows")
+        torch.cuda.synchronize()
+        return out
+
+    def _attn_map_request(self, attn_map, prompt_len: Optional[int]):
+        """`attn_map=` of a generation call -> the window it records with (None: not asked), the bank switched on.  prompt_len None
+        (a stream of clips whose prompts differ): keys=None is the engine's whole context."""
+        if attn_map is None:
+            return None
+        am = AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
+        W = am[0] if am[0] is not None else AM.window_for(self.c.max_ctx if prompt_len is None else prompt_len)
+        self._attn_map_on(W, am[1])
+        return W
+
+    def _outputs(self, lpn, amw):
+        """`outputs(lpn)`, and with attn_map= asked a dict per slot (an ids list becomes dict(ids=...)) that also holds attn_map
+        float32 [n_tokens, window]"""
+        out = self.outputs(lpn)
+        if amw is None:
+            return out
+        state = self.attn_map_state()
+        res = []
+        for b, r in enumerate(out):
+            r = dict(r) if isinstance(r, dict) else dict(ids=r)
+            r["attn_map"] = state[b, :len(r["ids"])].copy()
+            res.append(r)
+        return res
+
     # ------------------------------------------------------------------ sampling
     def _sampling_on(self):
         """The first sampling request switches the ctx's token pick to sample_advance_kernel (decode graphs are re-captured once);
@@ -1193,7 +1285,7 @@ class AuroraCapEngine:
 
     def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
                  sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None,
-                 logit_rules: Optional[dict] = None, stop=None):
+                 logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
         """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
         sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
         the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours.
@@ -1208,8 +1300,13 @@ class AuroraCapEngine:
         sequence also ends behind a token that is one of its stop ids, behind one whose bytes complete one of its stop strings
         (`set_stop_vocab` first), or when it holds its own max_new_tokens - decided on the device behind every pick, as
         `aurora_amd.stopping` defines it; the token that stops it stays in the output and `stopping.finish_reason` names the reason
-        from the ids.  None or all-neutral records: exactly the path of a call without the argument."""
+        from the ids.  None or all-neutral records: exactly the path of a call without the argument.
+        attn_map=dict(keys=W or None, layers=None or a list): each result is a dict that also holds attn_map float32 [len, W] - row i
+        the attention of the decode step that picked token i over keys [0, W) of its context, mean over the layers (None = all) and
+        all heads, as `aurora_amd.attn_map` defines it; row 0 (the prefill's token) is zeros.  keys=None: the longest prompt rounded
+        up to 64.  The ids are the same.  None: no extra work."""
         lpn = check_logprobs(logprobs)
+        amw = None if attn_map is None else self._attn_map_request(attn_map, max(seq_lens) if len(seq_lens) else 1)
         B = len(embeds_list)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
@@ -1236,14 +1333,16 @@ class AuroraCapEngine:
             done += n
             if may_end and self.unfinished() == 0:
                 break
-        return self.outputs(lpn)
+        return (self.outputs(lpn) if amw is None else self._outputs(lpn, amw))
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
                     eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None,
-                    logit_rules: Optional[dict] = None, stop: Optional[dict] = None):
-        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules / stop: as
-        in `generate`."""
+                    logit_rules: Optional[dict] = None, stop: Optional[dict] = None, attn_map: Optional[dict] = None):
+        """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules / stop /
+        attn_map: as in `generate`."""
         check_logprobs(logprobs)
+        if attn_map is not None:
+            AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
         LR.check_logit_rules(logit_rules)
         if stop is not None:
             self._stop_records(stop, 1, max_new_tokens)
@@ -1251,12 +1350,13 @@ class AuroraCapEngine:
         vis = self.vit_encode(pixels, r)
         emb, L = self.project_splice(vis, input_ids)
         return self.generate([emb], [L], max_new_tokens, eos_id, sampling=sampling, streams=[stream], logprobs=logprobs,
-                             logit_rules=logit_rules, **({} if stop is None else dict(stop=stop)))[0]
+                             logit_rules=logit_rules, **({} if stop is None else dict(stop=stop)),
+                             **({} if attn_map is None else dict(attn_map=attn_map)))[0]
 
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
                       streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None,
-                      logit_rules: Optional[dict] = None, stop=None):
+                      logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
@@ -1270,8 +1370,11 @@ class AuroraCapEngine:
         unshared path.  The same ids either way; share=None is exactly the path above.
         logprobs=n: a dict per clip instead of its ids, as in `generate`.
         logit_rules: one dict for every clip of the call, as in `generate` (each clip's own generated tokens are its history).
-        stop: one dict for every clip, or a list with one dict or None per clip, as in `generate`; siblings get theirs like any clip."""
+        stop: one dict for every clip, or a list with one dict or None per clip, as in `generate`; siblings get theirs like any clip.
+        attn_map: as in `generate` - a dict per clip with its attn_map; keys=None is the longest spliced prompt rounded up to 64."""
         lpn = check_logprobs(logprobs)
+        if attn_map is not None:
+            AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
         B = len(clips)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
@@ -1307,6 +1410,7 @@ class AuroraCapEngine:
             self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
+        amw = None if attn_map is None else self._attn_map_request(attn_map, max(p["seq_len"] for p in plans))
         self.begin_batch(B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         self._begin_rules(rules, B)
@@ -1356,15 +1460,18 @@ class AuroraCapEngine:
             done += n
             if may_end and self.unfinished() == 0:
                 break
-        return self.outputs(lpn)
+        return (self.outputs(lpn) if amw is None else self._outputs(lpn, amw))
 
     def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
                         eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None,
-                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None):
+                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
         """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
         (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs / logit_rules: as
-        in `generate`; stop: one dict for every prompt, or a list with one dict or None per prompt."""
+        in `generate`; stop: one dict for every prompt, or a list with one dict or None per prompt; attn_map: as in `caption_batch`,
+        per chunk."""
         check_logprobs(logprobs)
+        if attn_map is not None:
+            AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
         LR.check_logit_rules(logit_rules)
         prompts = [list(ids) for ids in list_of_input_ids]
         stops = None if stop is None else self._stop_records(stop, len(prompts), max_new_tokens)
@@ -1376,6 +1483,7 @@ class AuroraCapEngine:
                                       streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk),
                                       **({} if logprobs is None else dict(logprobs=logprobs)),
                                       **({} if logit_rules is None else dict(logit_rules=logit_rules)),
+                                      **({} if attn_map is None else dict(attn_map=attn_map)),
                                       **({} if stops is None else dict(stop=stops[c0:c0 + len(chunk)])))
         return out
 
@@ -1403,7 +1511,7 @@ class AuroraCapEngine:
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
                        sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None,
-                       logit_rules: Optional[dict] = None, stop=None):
+                       logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -1435,7 +1543,10 @@ class AuroraCapEngine:
         (in the overlapped mode: when the clip's front end is prepared, so that a rejected record is the clip's own error).  A
         request's own max_new_tokens frees its slot at the next check after it is reached.  A re-filled slot gets its record where
         it gets its sampling and logit-rule records, in both modes and for sibling front ends too.  A callable counts as asking: the
-        option is flipped when the call starts, since front-end graphs cannot be dropped while clips are staged behind them."""
+        option is flipped when the call starts, since front-end graphs cannot be dropped while clips are staged behind them.
+        attn_map: as in `generate` - yields (index, dict) with the clip's attn_map, the rows of a caption run alone, in both modes; a
+        re-filled slot's rows are cleared where its length is.  keys=None: the engine's whole context rounded up to 64 (the prompts of
+        a stream differ)."""
         lpn = check_logprobs(logprobs)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
@@ -1453,6 +1564,7 @@ class AuroraCapEngine:
             self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
+        amw = None if attn_map is None else self._attn_map_request(attn_map, None)
         B = self.max_batch if slots is None else slots
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"slots={B} for an engine built with max_batch={self.max_batch}")
@@ -1466,7 +1578,7 @@ class AuroraCapEngine:
             if self.spare_slots - n_hold < 1:
                 raise ValueError("caption_stream(overlap=True) needs an engine built with spare_slots >= 1 beyond its prefix_cache")
             yield from self._caption_stream_overlapped(clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus,
-                                                       front_graph, samp, stream_of, share_key, holders, lpn, rules, stop_of)
+                                                       front_graph, samp, stream_of, share_key, holders, lpn, rules, stop_of, amw)
             return
         self.begin_batch(B, max_new_tokens, eos_id)
         for s in range(B):
@@ -1524,7 +1636,7 @@ class AuroraCapEngine:
             lens, fin = self.slot_state()
             done = [s for s in range(B) if owner[s] is not None and fin[s]]
             if done:
-                out = self.outputs(lpn)
+                out = (self.outputs(lpn) if amw is None else self._outputs(lpn, amw))
                 for s in done:
                     yield owner[s], out[s]
                     owner[s] = None
@@ -1622,7 +1734,7 @@ class AuroraCapEngine:
         return fg.embeds, ((fg.stride, fg.lens) if pb else plan["seq_len"]), fg
 
     def _caption_stream_overlapped(self, clips, token_kept_ratio, max_new_tokens, eos_id, B, check_every, on_error, front_cus, front_graph=True,
-                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None, rules=None, stop_of=None):
+                                   samp=None, stream_of=None, share_key=None, holders=None, lpn=None, rules=None, stop_of=None, amw=None):
         from collections import deque
         sD = torch.cuda.current_stream(self.dev)
         sF, sDm = self._masked_streams(front_cus)
@@ -1739,7 +1851,7 @@ class AuroraCapEngine:
                 lens, fin = self.slot_state()
                 done = [s for s in range(B) if owner[s] is not None and fin[s]]
                 if done:
-                    out = self.outputs(lpn)
+                    out = (self.outputs(lpn) if amw is None else self._outputs(lpn, amw))
                     for s in done:
                         yield owner[s], out[s]
                         owner[s] = None

@@ -16,13 +16,15 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
-from .engine import AuroraCapEngine
+from .engine import AuroraCapEngine, splice_rows, tokens_at_layer
 from .logit_rules import KEYS as LOGIT_RULE_KEYS, check_logit_rules
 from . import stopping as ST
 from .sampling import DEFAULT_TOP_K, check_sampling
 from .scoring import check_logprobs
+from . import attn_map as AM
 
 DEFAULT_IMAGE_TOKEN = "<image>"          # src/xtuner/xtuner/utils/constants.py:5
 IMAGE_TOKEN_INDEX = -200                 # constants.py:4
@@ -94,10 +96,16 @@ class AuroraEncoder:
 class GenerateOutput:
     """What `_LLM.generate(return_dict_in_generate=True)` returns: `sequences` LongTensor [1, n] (what the plain call returns) and,
     with output_logprobs=True, `token_logprobs` float32 [1, n], `top_ids` long [1, n, k], `top_logprobs` float32 [1, n, k]
-    (k = top_logprobs; `aurora_amd.scoring.token_logprobs` is the definition) - else None."""
+    (k = top_logprobs; `aurora_amd.scoring.token_logprobs` is the definition) - else None.  With output_attentions=True,
+    `prompt_attention` float32 [1, n, W]: row i the attention of the step that picked token i over keys [0, W) of its context, mean
+    over layers and heads (`aurora_amd.attn_map`; row 0, the prefill's token, is zeros); and, when the visual rows were passed
+    (`vis_rows`, what `AuroraModel.forward` adds with data["output_attentions"]), `visual_attention` float32 [n, nvis] - its columns at
+    the visual tokens - and `visual_share` float32 [n], its row sums: how much of each token's attention went to the visual prefix."""
 
-    def __init__(self, sequences, token_logprobs=None, top_ids=None, top_logprobs=None):
+    def __init__(self, sequences, token_logprobs=None, top_ids=None, top_logprobs=None, prompt_attention=None, visual_attention=None,
+                 visual_share=None):
         self.sequences, self.token_logprobs, self.top_ids, self.top_logprobs = sequences, token_logprobs, top_ids, top_logprobs
+        self.prompt_attention, self.visual_attention, self.visual_share = prompt_attention, visual_attention, visual_share
 
 
 def split_stop_arguments(eos_token_id, stop_strings=None, stop_token_ids=None):
@@ -136,9 +144,14 @@ class _LLM:
                  output_logprobs: bool = False, top_logprobs: int = 0, return_dict_in_generate: bool = False,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                  min_new_tokens: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_ids=None, merge_map=None,
-                 merge_sizes=None, **unused):
+                 merge_sizes=None, output_attentions: bool = False, attention_keys: Optional[int] = None, attention_layers=None,
+                 vis_rows=None, **unused):
         """`merge_map` / `merge_sizes` (what `AuroraModel.forward` adds with data["output_merge_map"]) are accepted and ignored, so
         `generate(**out, ...)` keeps working.
+        output_attentions=True (transformers' flag; needs return_dict_in_generate=True, ValueError otherwise): the result carries
+        `prompt_attention` [1, n, W] - W = attention_keys, a multiple of 64, or the prompt length rounded up to 64 -, averaged over
+        attention_layers (None = all) and all heads, and with `vis_rows` also `visual_attention` / `visual_share`.  The ids are
+        the same.
         do_sample=False: greedy; `temperature` / `top_p` are ignored, as transformers ignores them.  do_sample=True: seeded
         sampling with `temperature` (> 0), `top_p` and `top_k`.  The default temperature stays 0.0 (what every reference caller
         passes for greedy), not transformers' 1.0, so do_sample=True without a temperature raises ValueError: pass one.  The
@@ -164,7 +177,12 @@ class _LLM:
             raise ValueError("stop_strings needs tokenizer= as well: the strings are matched on the text the tokens decode to")
         if output_logprobs and not return_dict_in_generate:
             raise ValueError("output_logprobs=True needs return_dict_in_generate=True (the plain call returns the ids tensor alone)")
+        if output_attentions and not return_dict_in_generate:
+            raise ValueError("output_attentions=True needs return_dict_in_generate=True (the plain call returns the ids tensor alone)")
         lpn = check_logprobs(top_logprobs) if output_logprobs else None
+        am = dict(keys=attention_keys, layers=attention_layers) if output_attentions else None
+        if am is not None:
+            AM.check_attn_map(am, self.config["num_hidden_layers"])
         if inputs_embeds is None:
             raise ValueError("generate() on this path takes inputs_embeds (the output of model(data, mode='inference'))")
         if num_beams != 1:
@@ -191,13 +209,24 @@ class _LLM:
             kw["logit_rules"] = rules
         if stop is not None:
             kw["stop"] = stop
-        if lpn is None:
+        if am is not None:
+            kw["attn_map"] = am
+        if lpn is None and am is None:
             ids = self._e.generate([pad], [L], n, eos_id=eos, **kw)[0]
             seq = torch.tensor([ids], dtype=torch.long)
             return GenerateOutput(seq) if return_dict_in_generate else seq
-        r = self._e.generate([pad], [L], n, eos_id=eos, logprobs=lpn, **kw)[0]
-        return GenerateOutput(torch.tensor([r["ids"]], dtype=torch.long), torch.from_numpy(r["token_logprobs"]).unsqueeze(0),
-                              torch.from_numpy(r["top_ids"].astype("int64")).unsqueeze(0), torch.from_numpy(r["top_logprobs"]).unsqueeze(0))
+        r = self._e.generate([pad], [L], n, eos_id=eos, **({} if lpn is None else dict(logprobs=lpn)), **kw)[0]
+        out = GenerateOutput(torch.tensor([r["ids"]], dtype=torch.long))
+        if lpn is not None:
+            out.token_logprobs, out.top_logprobs = torch.from_numpy(r["token_logprobs"]).unsqueeze(0), torch.from_numpy(r["top_logprobs"]).unsqueeze(0)
+            out.top_ids = torch.from_numpy(r["top_ids"].astype("int64")).unsqueeze(0)
+        if am is not None:
+            out.prompt_attention = torch.from_numpy(r["attn_map"]).unsqueeze(0)
+            if vis_rows is not None:
+                rows = vis_rows.cpu().numpy() if torch.is_tensor(vis_rows) else vis_rows
+                va = AM.visual(r["attn_map"], rows)
+                out.visual_attention, out.visual_share = torch.from_numpy(va), torch.from_numpy(va.sum(1, dtype=va.dtype))
+        return out
 
 
 class AuroraModel:
@@ -220,7 +249,7 @@ class AuroraModel:
         return model
 
     def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None,
-                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None):
+                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
@@ -231,8 +260,12 @@ class AuroraModel:
         logit_rules=dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0): the three rules of `llm.generate` for
         every clip of the call, each over its own generated tokens (not its prompt).
         stop=dict(token_ids=(), strings=(), max_new_tokens=0) for every clip, or a list with one dict or None per clip: stop ids,
-        stop strings (`llm.use_tokenizer(tok)` first) and a budget of the clip's own (AuroraCapEngine.generate)."""
+        stop strings (`llm.use_tokenizer(tok)` first) and a budget of the clip's own (AuroraCapEngine.generate).
+        attn_map=dict(keys=W or None, layers=None or a list): a dict per clip that also holds attn_map float32 [n, W]
+        (AuroraCapEngine.generate), visual_attention [n, nvis] - its columns at the clip's visual tokens - and visual_share [n]."""
         check_logprobs(logprobs)
+        if attn_map is not None:
+            AM.check_attn_map(attn_map, self.llm.config["num_hidden_layers"])
         rules = check_logit_rules(logit_rules)
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
@@ -254,8 +287,24 @@ class AuroraModel:
                 kw["logit_rules"] = rules
             if stop is not None:
                 kw["stop"] = stop if isinstance(stop, dict) else stop[c0:c0 + len(group)]
-            out.extend(self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw))
+            if attn_map is not None:
+                kw["attn_map"] = attn_map
+            res = self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw)
+            if attn_map is not None:
+                for (px, ids), r in zip(group, res):
+                    self._add_visual(r, px.shape, ids)
+            out.extend(res)
         return out
+
+    def _add_visual(self, r: dict, shape, ids):
+        """visual_attention [n, nvis] and visual_share [n] beside a result's attn_map: its columns at the context positions of the
+        clip's visual tokens under the current merge ratio (the splice plan's vis_rows), and their row sums"""
+        e = self.engine
+        tr = e.tome_r(self.visual_encoder.visual_token_merge_ratio, shape[-2], shape[-1])
+        t0 = (shape[-2] // e.v["patch_size"]) * (shape[-1] // e.v["patch_size"]) + 1
+        rows = splice_rows(ids, shape[0], tokens_at_layer(t0, tr, e.v["num_hidden_layers"] - 1) - 1)["vis_rows"]
+        r["visual_attention"] = AM.visual(r["attn_map"], rows)
+        r["visual_share"] = r["visual_attention"].sum(1, dtype=np.float32)
 
     def loglikelihood_batch(self, items, share: bool = True):
         """Log-likelihood of given continuations: items = [(pixel_values [f, c, h, w], context ids with -200 markers, continuation
@@ -293,7 +342,8 @@ class AuroraModel:
                                   **({} if stop is None else dict(stop=stop)))
 
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
-                       overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None, stop=None):
+                       overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None, stop=None,
+                       attn_map: Optional[dict] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): yields (index, new-token ids) as captions
         finish (EOS or max_new_tokens), re-filling freed KV slots with the next clips.  Per-clip results equal the
         one-at-a-time calls.  overlap (default: on for an engine with spare KV sequences): the next clips' front ends run
@@ -302,17 +352,31 @@ class AuroraModel:
         share_key: callable index -> key | None; clips of equal key are the same visual input (engine built with prefix_cache >= 1).
         logit_rules: as in `caption_batch`; a clip's history starts empty in whatever slot it lands.
         stop: one dict for every clip, or a callable index -> dict | None (AuroraCapEngine.caption_stream): a clip with a budget of
-        its own gives its slot back when it is reached."""
+        its own gives its slot back when it is reached.
+        attn_map: as in `caption_batch` - yields (index, dict) with attn_map, visual_attention and visual_share."""
         rules = check_logit_rules(logit_rules)
+        if attn_map is not None:
+            AM.check_attn_map(attn_map, self.llm.config["num_hidden_layers"])
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         n = min(max_new_tokens, self.engine.max_new_tokens)
-        it = ((px, ids.tolist() if torch.is_tensor(ids) else list(ids)) for px, ids in clips)
-        yield from self.engine.caption_stream(it, self.visual_encoder.visual_token_merge_ratio, n, eos, check_every=check_every,
-                                              on_error=on_error, overlap=overlap,
-                                              **(dict(share_key=share_key) if share_key is not None else {}),
-                                              **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}),
-                                              **(dict(logit_rules=rules) if rules is not None else {}),
-                                              **(dict(stop=stop) if stop is not None else {}))
+        seen = {}                                                                 # index -> (pixel shape, ids) of the clips in flight (attn_map)
+
+        def it():
+            for k, (px, ids) in enumerate(clips):
+                ids = ids.tolist() if torch.is_tensor(ids) else list(ids)
+                if attn_map is not None:
+                    seen[k] = (tuple(px.shape), ids)
+                yield px, ids
+        for k, r in self.engine.caption_stream(it(), self.visual_encoder.visual_token_merge_ratio, n, eos, check_every=check_every,
+                                               on_error=on_error, overlap=overlap,
+                                               **(dict(share_key=share_key) if share_key is not None else {}),
+                                               **(dict(sampling=sampling, stream_of=stream_of) if sampling is not None else {}),
+                                               **(dict(logit_rules=rules) if rules is not None else {}),
+                                               **(dict(stop=stop) if stop is not None else {}),
+                                               **(dict(attn_map=attn_map) if attn_map is not None else {})):
+            if attn_map is not None:
+                self._add_visual(r, *seen.pop(k))
+            yield k, r
 
     def __call__(self, data: dict, data_samples=None, mode: str = "loss"):
         return self.forward(data, data_samples, mode)
@@ -331,6 +395,8 @@ class AuroraModel:
         ids = data["input_ids"]
         ids = ids[0].tolist() if torch.is_tensor(ids) else list(ids[0])
         want_map = bool(data.get("output_merge_map"))
+        want_rows = bool(data.get("output_attentions"))         # the context positions of the visual tokens, for `llm.generate(vis_rows=...)`
+        vis_rows = None
         maps = None
         enc = (lambda p: self.visual_encoder(p, output_merge_map=True)) if want_map else self.visual_encoder
         if self.slowfast and px.shape[1] != 1:                                    # aurora.py:223-246
@@ -344,14 +410,20 @@ class AuroraModel:
             counts = [high.shape[1]] + [low.shape[1]] * low.shape[0]
             plan = self.engine.splice_plan(ids, px.shape[1], counts, strict=True)  # utils.py:297-431: marker i <- frame i
             embeds, L = self.engine.project_splice(flat, plan=plan)
+            if want_rows:
+                vis_rows = splice_rows(ids, px.shape[1], counts, strict=True)["vis_rows"]
         else:
             vis = enc(px[0])                                                      # aurora.py:249-253
             if want_map:
                 vis, vmap, vsz = vis
                 maps = (vmap, list(vsz))
             embeds, L = self.engine.project_splice(vis, ids)                     # aurora.py:254-258
+            if want_rows:
+                vis_rows = splice_rows(ids, vis.shape[0], vis.shape[1])["vis_rows"]
         out = {"input_ids": None, "position_ids": None, "attention_mask": None, "past_key_values": None,
                "inputs_embeds": embeds[:L].unsqueeze(0), "labels": None}          # utils.py:288-295
         if want_map:                      # merge_map int32 [f, gh, gw], merge_sizes: f tensors fp32 [tokens of that frame] (merge_map.py)
             out["merge_map"], out["merge_sizes"] = maps
+        if want_rows:
+            out["vis_rows"] = torch.from_numpy(vis_rows)
         return out

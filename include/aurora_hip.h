@@ -539,6 +539,35 @@ int aur_slot_collect_logprobs(aur_ctx* ctx, int32_t slot0, int32_t nslots, float
 int aur_token_logprob_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t vocab, const int32_t* tokens_dev, int32_t top_n,
                            float* lp_out, int32_t* top_ids_out, float* top_lp_out, void* stream);
 
+/* ---- attention of every GENERATED token over a prefix window of its context (transformers'
+ * generate(output_attentions=True), averaged).  aurora_amd/attn_map.py is the definition in numpy.
+ * The decode step that picks generated token i >= 1 of a slot (token 0 is the prefill's and has no record) attends, in every layer l and
+ * head h, with the roped fp16 query it wrote to keys [0, npos = pos + 1) of the slot's pages - the one it has just written included:
+ * P[l, h, j] = softmax_j(scale q . k_j), the distribution the decode attention itself uses, evaluated in fp32.  The record is
+ * A[i, j] = mean over the selected layers and all heads of P[l, h, j] for j < min(window, npos), and exactly 0.0 for the other j < window.
+ * Row 0 of a slot and every row at or beyond its generated length are zeros; with window >= npos a recorded row sums to 1.
+ * window: a multiple of 64 in [64, max_ctx rounded up to 64].  layer_mask: bit l = layer l (at most 64 layers), 0 = all.
+ * The state of one bank lives in a CALLER-OWNED device buffer of aur_attn_map_bytes bytes (256-byte aligned: records fp32
+ * [max_batch][max_new_tokens][window], then the recorder's scratch): nothing is allocated here, aur_workspace_bytes does not grow, and a
+ * process that never asks launches exactly what it did.  aur_attn_map_enable acts on the CURRENT bank: clears the records on the stream
+ * and, from then on, every decode step - captured or eager - launches the recorder (attn_map.hip: two kernels, one more pass over K)
+ * behind the QKV projection of each selected layer.  Slots that are finished or full write nothing.  The record is a function of the
+ * slot's own q and K alone: bitwise the same at any batch, slot, bank, split geometry ("dec_attn_pps", "dec_attn_local") or launch
+ * form.  buf_dev == NULL turns it off again.  The choice is frozen in the bank's captured decode graphs, which the call drops;
+ * AUR_ERR_STATE inside aur_graph_begin / aur_graph_end.  aur_begin_batch, aur_slot_reset and the commits clear the rows of the slots
+ * whose lengths they clear (a caller's capture that holds one of them is re-captured by the caller).
+ * aur_get_attn_map (synchronises, like aur_get_logprobs): map_host fp32 [batch * max_new_tokens * window], max_new_tokens the batch's.
+ * aur_slot_collect_attn_map: the same for slots [slot0, slot0 + nslots) device-to-device, enqueue-only and recordable.
+ * aur_attn_map_rows: the kernels alone on caller rows, beside aur_attn_decode_rows and with its arguments: one layer, all heads, row b of
+ * out fp32 [rows, window] is the record of row b at position pos_dev[b].  scratch: aur_attn_map_rows_scratch_bytes(ctx, kx, window). */
+int64_t aur_attn_map_bytes(const aur_ctx* ctx, int32_t window);      /* -1: a bad window */
+int aur_attn_map_enable(aur_ctx* ctx, int32_t window, uint64_t layer_mask, void* buf_dev, int64_t nbytes, void* stream);
+int aur_get_attn_map(aur_ctx* ctx, float* map_host, void* stream);
+int aur_slot_collect_attn_map(aur_ctx* ctx, int32_t slot0, int32_t nslots, float* out_dev, void* stream);
+int64_t aur_attn_map_rows_scratch_bytes(const aur_ctx* ctx, int32_t kx, int32_t window);
+int aur_attn_map_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, const void* w_packed, int32_t npad, const int32_t* pos_dev,
+                      int32_t rope, void* scratch, int64_t scratch_bytes, int32_t window, float* out, void* stream);
+
 /* Tuning knobs.  Invalidate the captured decode graphs (of every bank): "decode_fused_reduce" 0 (default: the split-K residual projections are followed
  * by a reduce launch) / 1 (the last-arriving split reduces inside the kernel; bitwise the same), "dec_attn_local" 1 (default: on engines
  * of 8-15 slots x 32 heads the splits of a (sequence, head) are the waves of one attention workgroup, joined through LDS) / 0

@@ -68,7 +68,29 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--merge_vis', default=None, metavar='OUT.png',
                         help='write the frames side by side with every patch filled with the mean colour of its merged group and a line '
                              'between neighbouring patches of different groups')
+    # which visual tokens each generated token looked at (aurora_amd.attn_map); neither flag changes the caption line
+    parser.add_argument('--attn_map', default=None, metavar='OUT.npz',
+                        help='write, per generated token, its attention over the prompt (mean over layers and heads): attn_map float32 '
+                             '[tokens, keys], vis_rows, visual_attention [tokens, visual tokens], visual_share [tokens] and ids')
+    parser.add_argument('--attn_vis', default=None, metavar='OUT.png',
+                        help='write one row of heat maps per generated token, one tile per frame: each visual token\'s attention spread '
+                             'over the patches it stands for (the merge map of the same run)')
     return parser
+
+
+def write_attn_outputs(args, out, output):
+    """--attn_map / --attn_vis: the record `llm.generate(output_attentions=True)` returned, as an npz and as heat maps over the patch grid
+    (`attn_map.to_patches` with the merge map of the same run, `attn_map.render`; host work)."""
+    from aurora_amd import attn_map as AMAP
+    va = out.visual_attention.numpy()
+    if args.attn_map:
+        with open(args.attn_map, "wb") as fh:
+            np.savez(fh, attn_map=out.prompt_attention[0].numpy(), vis_rows=output["vis_rows"].numpy(), visual_attention=va,
+                     visual_share=out.visual_share.numpy(), ids=out.sequences[0].numpy())
+    if args.attn_vis:
+        from PIL import Image
+        heat = AMAP.to_patches(va, output["merge_map"].cpu().numpy())
+        Image.fromarray(AMAP.render(heat, patch=max(1, 112 // heat.shape[-1]))).save(args.attn_vis)
 
 
 def write_merge_outputs(args, output, pixel_values, patch):
@@ -118,6 +140,9 @@ def main():
     want_map = args.merge_map is not None or args.merge_vis is not None
     if want_map and (args.extra_prompt or args.score is not None):
         sys.exit("error: --merge_map / --merge_vis go with one generated caption (not with --extra_prompt or --score)")
+    want_attn = args.attn_map is not None or args.attn_vis is not None
+    if want_attn and (args.extra_prompt or args.score is not None):
+        sys.exit("error: --attn_map / --attn_vis go with one generated caption (not with --extra_prompt or --score)")
     rule_args = {k: getattr(args, k) for k in ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens") if getattr(args, k) is not None}
     try:
         from aurora_amd.logit_rules import check_logit_rules
@@ -223,8 +248,10 @@ def main():
         for ids in outs:
             print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
         return
-    if want_map:
+    if want_map or args.attn_vis is not None:        # the heat maps spread each visual token over the patches it stands for
         data["output_merge_map"] = True
+    if want_attn:
+        data["output_attentions"] = True
     output = model(data, mode="inference")
     if want_map:
         write_merge_outputs(args, output, data["pixel_values"], model.visual_encoder.config["patch_size"])
@@ -233,11 +260,14 @@ def main():
                               num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, **sample, **rule_args,
                               **(dict(stop_strings=args.stop, tokenizer=tokenizer) if args.stop else {}),
                               **(dict(stop_token_ids=args.stop_token_id) if args.stop_token_id else {}),
-                              **(dict(return_dict_in_generate=True, output_logprobs=True, top_logprobs=args.logprobs)
-                                 if args.logprobs is not None else {}))
+                              **(dict(return_dict_in_generate=True) if args.logprobs is not None or want_attn else {}),
+                              **(dict(output_logprobs=True, top_logprobs=args.logprobs) if args.logprobs is not None else {}),
+                              **(dict(output_attentions=True) if want_attn else {}))
     lp_out = None
-    if args.logprobs is not None:
-        lp_out, cont = cont, cont.sequences
+    if want_attn:
+        write_attn_outputs(args, cont, output)
+    if args.logprobs is not None or want_attn:
+        lp_out, cont = (cont if args.logprobs is not None else None), cont.sequences
     if tokenizer is None:
         print(cont[0].tolist())
     else:
