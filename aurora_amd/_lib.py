@@ -49,6 +49,11 @@ class AurLogitRules(C.Structure):
     _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int32), ("min_new_tokens", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AurGuidance(C.Structure):
+    """aur_guidance: one slot's guidance record (aurora_amd.guidance.RECORD is the numpy form of the same layout)"""
+    _fields_ = [("scale", C.c_float), ("partner", C.c_int32)]
+
+
 class AurStopRules(C.Structure):
     """aur_stop_rules: one slot's stop conditions (aurora_amd.stopping.RECORD is the numpy form of the same layout)"""
     _fields_ = [("max_new_tokens", C.c_int32), ("n_token_ids", C.c_int32), ("n_strings", C.c_int32), ("reserved", C.c_int32),
@@ -124,6 +129,8 @@ SIGNATURES = {
     "aur_slot_logit_rules": (C.c_int, [_P, _I, _I, _P, _P]),
     "aur_logit_rules_rows": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
     "aur_slot_stop": (C.c_int, [_P, _I, _I, _P, _P]),
+    "aur_slot_guidance": (C.c_int, [_P, _I, _I, _P, _P]),
+    "aur_guidance_rows": (C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P]),
     "aur_stop_vocab": (C.c_int, [_P, _P, _P, _I, _L]),
     "aur_stop_rows": (C.c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _L, _P]),
     "aur_attn_rows": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P]),

@@ -59,10 +59,34 @@ __device__ __forceinline__ int row_first_argmax(const float* __restrict__ lg, in
     return tok;
 }
 
+// The next input of slot b: x[b] = embed[tok] in x-fragment form, with its sum(x^2) (2^-28 fixed point).  By every thread of a workgroup
+// of at least 256 threads; sv: 256 floats of LDS.  The 256-thread loop and tree of rounds 1-3: same additions in the same order, same
+// bits, whoever calls (advance_tail for the slot that picked, guidance.hip guidance_follow_kernel for the partner that follows).
+__device__ __forceinline__ void embed_next_input(int b, int tok, const half_t* __restrict__ embed, int d, half_t* __restrict__ xf,
+                                                 unsigned long long* __restrict__ ssq, float* sv) {
+    const int tid = threadIdx.x;
+    float ss = 0.f;
+    if (tid < 256) {
+        for (int cidx = tid; cidx < (d >> 3); cidx += 256) {
+            const h8 v = *(const h8*)(embed + (int64_t)tok * d + cidx * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss += (float)v[j] * (float)v[j];
+            *(h8*)(xf + xfrag_piece(b, cidx * 8, d >> 5)) = v;
+        }
+        sv[tid] = ss;
+    }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {            // fixed-order tree: deterministic
+        if (tid < o) sv[tid] += sv[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) ssq_set(ssq, b, (unsigned long long)__float2ll_rn(sv[0] * SSQ_SCALE));
+}
+
 // Step bookkeeping for slot b once its token is known (every thread holds `tok`; called behind a barrier that protects sv): append
 // to out_ids unless the sequence already finished; EOS marks it finished; the next input x[b] = embed[token] is written in
 // x-fragment form together with sum(x^2) (2^-28 fixed point) for the first folded RMSNorm of the next step; pos[b] += advance_pos.
-// The embedding copy and its sum(x^2) keep the 256-thread loop and tree of rounds 1-3: same additions in the same order, same bits.
+// The embedding copy and its sum(x^2) are embed_next_input above.
 __device__ __forceinline__ void advance_tail(int b, int row, int tok, const half_t* __restrict__ embed, int d, int eos_id, int max_new,
                                              int32_t* __restrict__ out_ids, int32_t* __restrict__ out_len, int32_t* __restrict__ finished,
                                              int32_t* __restrict__ pos, half_t* __restrict__ xf, unsigned long long* __restrict__ ssq,
@@ -85,20 +109,5 @@ __device__ __forceinline__ void advance_tail(int b, int row, int tok, const half
         // decode steps (other slots still running, continuous batching) can never walk it past its KV allocation
         if (advance_pos && !was_finished) pos[b] += 1;
     }
-    float ss = 0.f;
-    if (tid < 256) {
-        for (int cidx = tid; cidx < (d >> 3); cidx += 256) {
-            const h8 v = *(const h8*)(embed + (int64_t)tok * d + cidx * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += (float)v[j] * (float)v[j];
-            *(h8*)(xf + xfrag_piece(b, cidx * 8, d >> 5)) = v;
-        }
-        sv[tid] = ss;
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {            // fixed-order tree: deterministic
-        if (tid < o) sv[tid] += sv[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) ssq_set(ssq, b, (unsigned long long)__float2ll_rn(sv[0] * SSQ_SCALE));
+    embed_next_input(b, tok, embed, d, xf, ssq, sv);
 }

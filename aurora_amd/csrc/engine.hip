@@ -92,6 +92,7 @@ struct aur_ctx {
     const uint8_t* stop_bytes = nullptr;
     int stop_vocab = 0;
     int64_t stop_nbytes = 0;
+    int guidance = 0;                                                           // 1: guidance_apply_kernel ahead of the logit rules, guidance_restore_kernel behind the pick, guidance_follow_kernel behind the stop check (the slots' aur_guidance records)
     int fused_reduce = 0;                                                       // 1: the split-K reduce runs inside the projection kernel
     // Generation banks: double-buffered per-batch state (KV slots, residual stream, sum(x^2), logits, outputs, graphs) so
     // that one batch can decode on one stream while the next batch's ViT + prefill run on another.  Every generation call
@@ -106,6 +107,8 @@ struct aur_ctx {
         int32_t* lr_cnt;                                     // entries of each slot's side list written by the last apply
         void* lr_save = nullptr;                             // side lists [max_batch][max_new_tokens + 1] of (index, original logit): allocated by option "logit_rules" 1
         aur_stop_rules* s_stop = nullptr;                    // per-slot stop records (aur_slot_stop) [max_batch]; all zero = neutral: allocated by option "stop_rules" 1
+        aur_guidance* s_guid = nullptr;                      // per-slot guidance records (aur_slot_guidance); all zero = neutral: allocated by option "guidance" 1
+        float* gd_save = nullptr;                            // the leaders' model rows while their guided rows stand in d_logits [max_batch][vocab]: allocated with the records
         int32_t* ptab;                                       // page-table rows of the bank's kv_seqs sequences
         // log-probabilities of generated tokens (aur_logprob_enable): the caller's buffer, nullptr = off.  lp_len [max_batch]: tokens of
         // slot b recorded so far; lp [b][max_new], lp_top_id / lp_top_lp [b][max_new][lp_top_n]: rows max_new apart, like s_ids
@@ -377,6 +380,8 @@ extern "C" void aur_destroy(aur_ctx* ctx) {
     for (auto& K : ctx->banks) {
         drop_graphs(K);
         if (K.lr_save) (void)hipFree(K.lr_save);
+        if (K.s_guid) (void)hipFree(K.s_guid);
+        if (K.gd_save) (void)hipFree(K.gd_save);
         if (K.s_stop) (void)hipFree(K.s_stop);
     }
     for (auto& ug : ctx->ugraphs)
@@ -1164,6 +1169,7 @@ extern "C" int aur_begin_batch(aur_ctx* ctx, int32_t batch, int32_t max_new_toke
     CK(hipMemsetAsync(K.s_samp, 0, (size_t)g.max_batch * sizeof(aur_sampling), s));      // every slot greedy until aur_slot_sampling says otherwise
     CK(hipMemsetAsync(K.s_rules, 0, (size_t)g.max_batch * sizeof(aur_logit_rules), s));  // every slot neutral until aur_slot_logit_rules says otherwise
     if (K.s_stop) CK(hipMemsetAsync(K.s_stop, 0, (size_t)g.max_batch * sizeof(aur_stop_rules), s));   // every slot without a stop request until aur_slot_stop says otherwise
+    if (K.s_guid) CK(hipMemsetAsync(K.s_guid, 0, (size_t)g.max_batch * sizeof(aur_guidance), s));     // every slot unguided until aur_slot_guidance says otherwise
     CK(hipMemsetAsync(K.s_ids, 0, (size_t)g.max_batch * g.max_new_tokens * 4, s));
     const size_t bp = (size_t)rup(g.max_batch, 16);       // unused fragment lanes must hold finite values
     CK(hipMemsetAsync(K.d_x, 0, bp * g.llm_hidden * 2, s));          // bank-owned buffers only: the other bank may be decoding
@@ -1179,6 +1185,8 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     const aur_config& g = ctx->cfg;
     const aur_ctx::Bank& K = ctx->bank();
     CK(launch_skinny(mk_lm_head(ctx, K.d_x, K.s_ssq_mlp, K.d_logits, K.batch, b0, b0 + nb), s));
+    // guidance: a leader's row becomes the contrast of its own and its partner's for the pick alone, ahead of the logit rules (transformers' order)
+    if (ctx->guidance) CK(launch_guidance_apply(K.d_logits, b0, nb, g.llm_vocab, g.max_batch, K.s_guid, K.gd_save, s));
     // logit rules: the affected entries of the rows are rewritten for the pick alone; behind it the rows are the model's again
     if (ctx->logit_rules)
         CK(launch_logit_rules_apply(K.d_logits, b0, nb, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
@@ -1189,6 +1197,7 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
         CK(launch_argmax_advance(K.d_logits, b0, nb, g.llm_vocab, ctx->l_embed, g.llm_hidden, K.eos, K.max_new, K.s_ids, K.s_len,
                                  K.s_fin, K.s_pos, K.d_x, K.s_ssq_mlp, advance, set_pos, s, set_pos_lens, len_cap));
     if (ctx->logit_rules) CK(launch_logit_rules_restore(K.d_logits, b0, nb, g.llm_vocab, K.max_new, K.lr_save, K.lr_cnt, s));
+    if (ctx->guidance) CK(launch_guidance_restore(K.d_logits, b0, nb, g.llm_vocab, K.s_guid, K.gd_save, s));
     // the log-probability of what was just picked, under the row it was picked from: a launch of its own behind the pick, which stays as it is
     if (K.lp_len)
         CK(launch_token_logprob(K.d_logits, b0, nb, g.llm_vocab, K.s_ids, K.s_len, K.max_new, K.lp_top_n, K.lp_len, K.lp, K.lp_top_id,
@@ -1197,6 +1206,10 @@ static int lm_head_and_advance(aur_ctx* ctx, int b0, int nb, int advance, int se
     if (ctx->stop_rules)
         CK(launch_stop_check(b0, nb, K.s_stop, K.s_ids, K.max_new, K.s_len, K.max_new, K.s_fin, ctx->stop_off, ctx->stop_bytes, ctx->stop_vocab,
                              ctx->stop_nbytes, s));
+    // guidance: the partner of every leader in the range takes the leader's token, length, finished flag and next input
+    if (ctx->guidance)
+        CK(launch_guidance_follow(b0, nb, g.llm_vocab, g.max_batch, K.s_guid, ctx->l_embed, g.llm_hidden, K.max_new, K.s_ids, K.s_len, K.s_fin,
+                                  K.d_x, K.s_ssq_mlp, s));
     return AUR_OK;
 }
 
@@ -1992,6 +2005,7 @@ extern "C" int aur_slot_reset(aur_ctx* ctx, int32_t slot, void* stream) {
     CK(hipMemsetAsync(K.s_ids + (int64_t)slot * K.max_new, 0, (size_t)K.max_new * 4, s));
     CK(hipMemsetAsync(K.s_rules + slot, 0, sizeof(aur_logit_rules), s));
     if (K.s_stop) CK(hipMemsetAsync(K.s_stop + slot, 0, sizeof(aur_stop_rules), s));
+    if (K.s_guid) CK(launch_guidance_clear(K.s_guid, ctx->cfg.max_batch, slot, 1, s));       // the slot's record, and a leader's whose partner it was
     return slot_records_clear(ctx, K, slot, 1, s);
 }
 extern "C" int aur_slot_retire(aur_ctx* ctx, int32_t slot, void* stream) {
@@ -2172,6 +2186,23 @@ extern "C" int aur_slot_logit_rules(aur_ctx* ctx, int32_t slot0, int32_t nslots,
     CK(hipMemcpyAsync(K.s_rules + slot0, rules_dev, (size_t)nslots * sizeof(aur_logit_rules), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return AUR_OK;
 }
+extern "C" int aur_slot_guidance(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_guidance* recs_dev, void* stream) {
+    if (int rc = slot_check(ctx, slot0, "aur_slot_guidance")) return rc;
+    const aur_ctx::Bank& K = ctx->bank();
+    if (!K.s_guid) return aur_fail(ctx, AUR_ERR_STATE, "aur_slot_guidance: set option \"guidance\" to 1 first");
+    if (nslots < 1 || slot0 + nslots > K.batch || !recs_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_slot_guidance: slots [%d, %d) outside the batch of %d, or null records", slot0, slot0 + nslots, K.batch);
+    CK(hipMemcpyAsync(K.s_guid + slot0, recs_dev, (size_t)nslots * sizeof(aur_guidance), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return AUR_OK;
+}
+extern "C" int aur_guidance_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const aur_guidance* recs_dev, float* save, int32_t mode,
+                                 void* stream) {
+    if (!ctx || !logits || !recs_dev || !save) return aur_fail(ctx, AUR_ERR_ARG, "aur_guidance_rows: null argument");
+    if (rows < 1 || rows > 65535 || vocab < 1 || mode < 0 || mode > 1)
+        return aur_fail(ctx, AUR_ERR_ARG, "aur_guidance_rows: rows %d outside [1, 65535], vocab %d < 1 or mode %d outside [0, 1]", rows, vocab, mode);
+    if (mode == 0) CK(launch_guidance_apply(logits, 0, rows, vocab, rows, recs_dev, save, (hipStream_t)stream));
+    else CK(launch_guidance_restore(logits, 0, rows, vocab, recs_dev, save, (hipStream_t)stream));
+    return AUR_OK;
+}
 extern "C" int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const int32_t* ids_dev, int32_t ids_stride,
                                     const int32_t* lens_dev, const aur_logit_rules* rules_dev, int32_t eos_id, int32_t restore, void* stream) {
     if (!ctx || !logits || !ids_dev || !lens_dev || !rules_dev) return aur_fail(ctx, AUR_ERR_ARG, "aur_logit_rules_rows: null argument");
@@ -2282,6 +2313,20 @@ extern "C" int aur_set_option(aur_ctx* ctx, const char* name, int64_t value) {
                 if (!ctx->banks[bk].lr_save)
                     CK(hipMalloc(&ctx->banks[bk].lr_save, (size_t)logit_rules_save_bytes(ctx->cfg.max_batch, ctx->cfg.max_new_tokens)));
         ctx->logit_rules = (int)value;
+    } else if (!strcmp(name, "guidance")) {
+        // whether the three launches stand around the pick is frozen inside the captured decode graphs, like "sampling": they are
+        // re-captured.  The records (neutral) and the save buffer are allocated here, once, outside any capture; they live as long as the ctx
+        if (value < 0 || value > 1) return aur_fail(ctx, AUR_ERR_ARG, "%s must be 0 or 1", name);
+        if (value)
+            for (int bk = 0; bk < 2; ++bk) {
+                aur_ctx::Bank& K = ctx->banks[bk];
+                if (!K.s_guid) {
+                    CK(hipMalloc((void**)&K.s_guid, (size_t)ctx->cfg.max_batch * sizeof(aur_guidance)));
+                    CK(hipMemset(K.s_guid, 0, (size_t)ctx->cfg.max_batch * sizeof(aur_guidance)));
+                }
+                if (!K.gd_save) CK(hipMalloc((void**)&K.gd_save, (size_t)ctx->cfg.max_batch * ctx->cfg.llm_vocab * sizeof(float)));
+            }
+        ctx->guidance = (int)value;
     } else if (!strcmp(name, "stop_rules")) {
         // whether stop_check_kernel follows the pick is frozen inside the captured decode graphs, like "sampling": they are re-captured.
         // The records are allocated here, once, outside any capture, neutral; they live as long as the ctx
@@ -2339,6 +2384,12 @@ extern "C" int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, d
             if (!ctx->logit_rules) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_rules needs option \"logit_rules\" 1");
             CK(launch_logit_rules_apply(K.d_logits, 0, K.batch, g.llm_vocab, K.s_rules, K.s_ids, K.max_new, K.s_len, K.eos, K.lr_save, K.lr_cnt, s));
             CK(launch_logit_rules_restore(K.d_logits, 0, K.batch, g.llm_vocab, K.max_new, K.lr_save, K.lr_cnt, s));
+        } else if (!strcmp(kernel, "dec_guid")) {              // guidance's three launches, on the logits and the records of the last step
+            if (!ctx->guidance) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_guid needs option \"guidance\" 1");
+            CK(launch_guidance_apply(K.d_logits, 0, K.batch, g.llm_vocab, g.max_batch, K.s_guid, K.gd_save, s));
+            CK(launch_guidance_restore(K.d_logits, 0, K.batch, g.llm_vocab, K.s_guid, K.gd_save, s));
+            CK(launch_guidance_follow(0, K.batch, g.llm_vocab, g.max_batch, K.s_guid, ctx->l_embed, d, K.max_new, K.s_ids, K.s_len, K.s_fin, K.d_x,
+                                      K.s_ssq_mlp, s));
         } else if (!strcmp(kernel, "dec_stop")) {              // the stop check alone, on the history and the records of the last step
             if (!ctx->stop_rules) return aur_fail(ctx, AUR_ERR_STATE, "aur_microbench: dec_stop needs option \"stop_rules\" 1");
             CK(launch_stop_check(0, K.batch, K.s_stop, K.s_ids, K.max_new, K.s_len, K.max_new, K.s_fin, ctx->stop_off, ctx->stop_bytes,

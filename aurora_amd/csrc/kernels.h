@@ -260,6 +260,16 @@ hipError_t launch_stop_check(int b0, int nb, const aur_stop_rules* rules, const 
                              int batch_max_new, int32_t* finished, const int32_t* offsets, const uint8_t* bytes, int vocab, int64_t nbytes,
                              hipStream_t s);
 
+// ---- guidance.hip: classifier-free guidance around the pick of slots [b0, b0 + nb).  recs [max_batch]: a leader's record names its
+// partner (clamped into [0, max_batch)); save fp32 [max_batch][vocab]: the leaders' model rows between apply and restore.  follow: the
+// partner takes the leader's newest token, out_len, finished and next input.  clear: records [s0, s0 + n) and their leaders' -> neutral
+struct aur_guidance;
+hipError_t launch_guidance_apply(float* logits, int b0, int nb, int vocab, int max_batch, const aur_guidance* recs, float* save, hipStream_t s);
+hipError_t launch_guidance_restore(float* logits, int b0, int nb, int vocab, const aur_guidance* recs, const float* save, hipStream_t s);
+hipError_t launch_guidance_follow(int b0, int nb, int vocab, int max_batch, const aur_guidance* recs, const half_t* embed, int d, int max_new,
+                                  int32_t* out_ids, int32_t* out_len, int32_t* finished, half_t* xf, unsigned long long* ssq, hipStream_t s);
+hipError_t launch_guidance_clear(aur_guidance* recs, int max_batch, int s0, int n, hipStream_t s);
+
 // ---- score.hip: log-probability of a target token under a logits row (+ the row's first argmax), and the row-list gather that feeds
 // any rows of a prefill pass to the pick path's lm_head (aur_llm_score_var)
 hipError_t launch_score_rows(const float* logits, int rows, int vocab, const int32_t* targets, float* logprob_out, int32_t* argmax_out,

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import guidance as GD
 from . import logit_rules as LR
 from . import stopping as ST
 from . import sampling as S
@@ -339,6 +340,8 @@ class AuroraCapEngine:
         self._sampling_mode = False                      # ctx option "sampling": flipped by the first sampling request, sticky
         self._samp_stage = None                          # device staging of aur_sampling records, one row per (bank, slot)
         self._rules_mode = False                         # ctx option "logit_rules": flipped by the first request with non-neutral rules, sticky
+        self._guid_mode = False                          # ctx option "guidance": flipped by the first guided request, sticky
+        self._guid_stage = None                          # device staging of aur_guidance records, one row per (bank, slot)
         self._rules_stage = None                         # device staging of aur_logit_rules records, one row per (bank, slot)
         self._stop_mode = False                          # ctx option "stop_rules": flipped by the first request with a non-neutral stop record, sticky
         self._stop_stage = None                          # device staging of aur_stop_rules records, one row per (bank, slot)
@@ -651,7 +654,7 @@ class AuroraCapEngine:
                 plan = self.splice_plan(input_ids, vis.shape[0], vis.shape[1])
             assert plan["n_kept"] == vis.shape[1] and plan["used"] <= vis.shape[0]
             seq_len, used = plan["seq_len"], plan["used"]
-            vflat = self._h(vis[:used]).reshape(used * plan["n_kept"], -1)
+            vflat = self._h(vis[:used]).reshape(used * plan["n_kept"], vis.shape[-1])      # used may be 0: a text-only splice
         rows = _rup(seq_len, 32) if stride is None else stride
         embeds = out if out is not None else torch.empty(rows, d, dtype=torch.float16, device=self.dev)
         assert embeds.shape[0] >= rows and embeds.is_contiguous()
@@ -760,22 +763,24 @@ class AuroraCapEngine:
     def decode(self, steps: int):
         check(self.ctx, self.L.aur_llm_decode(self.ctx, steps, self._stream()), "aur_llm_decode")
 
-    def outputs(self, logprobs: Optional[int] = None):
+    def outputs(self, logprobs: Optional[int] = None, count: Optional[int] = None):
         """The generated ids of every slot; with logprobs=n (a bank that records them, `_logprobs_on`) a dict per slot instead:
-        ids, token_logprobs float32 [len], top_ids int32 [len, n], top_logprobs float32 [len, n]."""
+        ids, token_logprobs float32 [len], top_ids int32 [len, n], top_logprobs float32 [len, n].  count: slots [0, count) only
+        (a guided call's leaders)."""
         ids = np.zeros((self._batch, self._max_new), np.int32)
         lens = np.zeros(self._batch, np.int32)
         check(self.ctx, self.L.aur_get_outputs(self.ctx, ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                                lens.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "aur_get_outputs")
-        out = [ids[b, : lens[b]].tolist() for b in range(self._batch)]
+        nb = self._batch if count is None else min(int(count), self._batch)
+        out = [ids[b, : lens[b]].tolist() for b in range(nb)]
         if logprobs is None:
             return out
         n = check_logprobs(logprobs)
         rec, lp, tid, tlp = self.token_logprob_state()
-        if (rec != lens).any():
+        if (rec[:nb] != lens[:nb]).any():
             raise RuntimeError(f"log-probability records {rec.tolist()} for generated lengths {lens.tolist()}: enabled in mid-generation?")
         return [dict(ids=out[b], token_logprobs=lp[b, :lens[b]].copy(), top_ids=tid[b, :lens[b], :n].copy(),
-                     top_logprobs=tlp[b, :lens[b], :n].copy()) for b in range(self._batch)]
+                     top_logprobs=tlp[b, :lens[b], :n].copy()) for b in range(nb)]
 
     def unfinished(self) -> int:
         n = C.c_int32(0)
@@ -1073,10 +1078,10 @@ class AuroraCapEngine:
         self._attn_map_on(W, am[1])
         return W
 
-    def _outputs(self, lpn, amw):
+    def _outputs(self, lpn, amw, count: Optional[int] = None):
         """`outputs(lpn)`, and with attn_map= asked a dict per slot (an ids list becomes dict(ids=...)) that also holds attn_map
         float32 [n_tokens, window]"""
-        out = self.outputs(lpn)
+        out = self.outputs(lpn, count)
         if amw is None:
             return out
         state = self.attn_map_state()
@@ -1159,6 +1164,62 @@ class AuroraCapEngine:
         """After begin_batch (which makes every slot neutral): the records of slots [0, B) for a call with logit rules."""
         if rules is not None:
             self.slot_logit_rules(0, LR.records(rules, B))
+
+    # ------------------------------------------------------------------ classifier-free guidance
+    def _guidance_on(self):
+        """The first guided request puts guidance_apply_kernel / guidance_restore_kernel around the ctx's token pick and
+        guidance_follow_kernel behind the stop check (decode graphs are re-captured once, the banks' records and save buffers are
+        allocated); slots whose record is neutral are not touched.  Sticky, like `_rules_on`.  A process that never asks never
+        gets here."""
+        if not self._guid_mode:
+            self._drop_front_graphs()
+            self.set_option("guidance", 1)
+            self._guid_mode = True
+
+    def slot_guidance(self, slot0: int, recs: np.ndarray):
+        """Give slots [slot0, slot0 + len(recs)) of the current bank their aur_guidance records (`guidance.records`): staged in
+        device memory and copied into the bank when the stream gets there - before the prefill / commit that picks the first token.
+        A leader's record names its partner; prefill the partner first, its row is what the leader's first pick contrasts with."""
+        recs = np.ascontiguousarray(recs, dtype=GD.RECORD)
+        n = len(recs)
+        if n < 1 or slot0 < 0 or slot0 + n > self.max_batch:
+            raise ValueError(f"slots [{slot0}, {slot0 + n}) outside an engine of {self.max_batch} slots")
+        if self._guid_stage is None:
+            self._guid_stage = torch.zeros(2 * self.max_batch, GD.RECORD.itemsize, dtype=torch.uint8, device=self.dev)
+        row0 = self._bank * self.max_batch + slot0
+        dst = self._guid_stage[row0: row0 + n]
+        dst.copy_(torch.from_numpy(recs.view(np.uint8).reshape(n, GD.RECORD.itemsize).copy()))     # torch's current stream: _stream() orders ours behind it
+        check(self.ctx, self.L.aur_slot_guidance(self.ctx, slot0, n, dst.data_ptr(), self._stream()), "aur_slot_guidance")
+
+    def guidance_rows(self, logits: torch.Tensor, recs: np.ndarray, restore: bool = False, b0: int = 0, nb: Optional[int] = None):
+        """The guidance kernels alone (aur_guidance_rows) on a copy of `logits` (fp32 [rows, vocab] on the device), one aur_guidance
+        record per row, partners being rows of the same buffer; the kernels see rows [b0, b0 + nb) alone (default: all), whose
+        partners must lie among them -> (rows, save) on the device: the whole buffer and the whole save buffer behind
+        guidance_apply_kernel (restore=False) or behind apply + restore (restore=True).  The save buffer starts as NaN with the bit
+        pattern 0x7fc0beef."""
+        assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2
+        rows, vocab = logits.shape
+        recs = np.ascontiguousarray(recs, dtype=GD.RECORD)
+        nb = rows - b0 if nb is None else int(nb)
+        assert len(recs) == rows and 0 <= b0 and nb >= 1 and b0 + nb <= rows
+        sub = recs[b0:b0 + nb].copy()
+        lead = (sub["scale"] > 0) & (sub["scale"] != 1) & np.isfinite(sub["scale"])
+        assert ((sub["partner"][lead] >= b0) & (sub["partner"][lead] < b0 + nb)).all(), "a partner outside the launched rows"
+        sub["partner"][lead] -= b0
+        rec_d = torch.from_numpy(sub.view(np.uint8).reshape(nb, GD.RECORD.itemsize).copy()).to(self.dev)
+        out = logits.clone().contiguous()
+        save = torch.full((rows, vocab), 0x7fc0beef, dtype=torch.int32, device=self.dev).view(torch.float32)
+        torch.cuda.synchronize()
+        for mode in ((0, 1) if restore else (0,)):
+            check(self.ctx, self.L.aur_guidance_rows(self.ctx, out[b0:].data_ptr(), nb, vocab, rec_d.data_ptr(), save[b0:].data_ptr(),
+                                                     mode, self._stream()), "aur_guidance_rows")
+        torch.cuda.synchronize()
+        return out, save
+
+    def _begin_guidance(self, gd: Optional[dict], pairs, count: int):
+        """After begin_batch (which makes every slot neutral): the records of slots [0, count) for a guided call."""
+        if gd is not None:
+            self.slot_guidance(0, GD.records(gd["scale"], pairs, count))
 
     # ------------------------------------------------------------------ stop conditions
     def set_stop_vocab(self, table):
@@ -1285,7 +1346,7 @@ class AuroraCapEngine:
 
     def generate(self, embeds_list, seq_lens, max_new_tokens: int, eos_id: Optional[int] = 2, check_every: int = 32,
                  sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None, logprobs: Optional[int] = None,
-                 logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
+                 logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None, guidance: Optional[dict] = None):
         """Generation for a batch of already-spliced prefixes (one KV slot per sequence): greedy, or with
         sampling=dict(temperature, top_k, top_p, seed) drawn as `aurora_amd.sampling` defines it; `streams` (default range(B)) are
         the sequences' request indices - a sequence's ids depend on (seed, its stream), not on its slot or its neighbours.
@@ -1304,10 +1365,23 @@ class AuroraCapEngine:
         attn_map=dict(keys=W or None, layers=None or a list): each result is a dict that also holds attn_map float32 [len, W] - row i
         the attention of the decode step that picked token i over keys [0, W) of its context, mean over the layers (None = all) and
         all heads, as `aurora_amd.attn_map` defines it; row 0 (the prefill's token) is zeros.  keys=None: the longest prompt rounded
-        up to 64.  The ids are the same.  None: no extra work."""
+        up to 64.  The ids are the same.  None: no extra work.
+        guidance=dict(scale=g, negative=[(embeds, seq_len), ...]), one negative prefix per sequence: classifier-free guidance as
+        `aurora_amd.guidance` defines it.  Sequence i decodes in slot i, its negative in slot B + i, in lock-step; ahead of every pick
+        - and of the logit rules - row i becomes g * (log_softmax(row i) - log_softmax(row B + i)) + log_softmax(row B + i), and the
+        token picked from it is appended to both.  A guided call needs 2 B <= max_batch.  The results are the B sequences' alone, in
+        every form; log-probabilities stay those of the model's conditional row.  None, or a scale of None / 1: exactly the path of
+        a call without the argument."""
         lpn = check_logprobs(logprobs)
         amw = None if attn_map is None else self._attn_map_request(attn_map, max(seq_lens) if len(seq_lens) else 1)
         B = len(embeds_list)
+        gd = GD.check_guidance(guidance)
+        pairs = None
+        if gd is not None:
+            negs = gd.get("negative")
+            if negs is None or len(negs) != B:
+                raise ValueError(f"guidance: `negative` must hold one (embeds, seq_len) per sequence ({B})")
+            pairs = GD.pair_slots(B, self.max_batch)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)
         stops = None if stop is None else self._stop_records(stop, B, max_new_tokens)
@@ -1319,10 +1393,16 @@ class AuroraCapEngine:
             self._stop_on()
         if lpn is not None:
             self._logprobs_on(lpn)
-        self.begin_batch(B, max_new_tokens, eos_id)
+        if gd is not None:
+            self._guidance_on()
+        self.begin_batch(B if gd is None else 2 * B, max_new_tokens, eos_id)
         self._begin_sampled(samp, streams, B)
         self._begin_rules(rules, B)
         self._begin_stop(stops, B)
+        if gd is not None:                                        # the partners first: a leader's first pick reads its partner's row
+            self._begin_guidance(gd, pairs, 2 * B)
+            for lead, part in pairs:
+                self.prefill(part, negs[lead][0], negs[lead][1])
         for b in range(B):
             self.prefill(b, embeds_list[b], seq_lens[b])
         may_end = eos_id is not None or stops is not None
@@ -1333,13 +1413,76 @@ class AuroraCapEngine:
             done += n
             if may_end and self.unfinished() == 0:
                 break
-        return (self.outputs(lpn) if amw is None else self._outputs(lpn, amw))
+        return (self.outputs(lpn, B) if amw is None else self._outputs(lpn, amw, B))
+
+    def _negative_ids(self, gd: dict, prompts: Sequence[Sequence[int]]) -> List[List[int]]:
+        """The negative prompt of every request of a guided caption call.  negative_ids None: the request's own prompt without its
+        image markers (the language prior alone); one list of ids: that prompt for every request; a list of lists: one each."""
+        neg = gd.get("negative_ids")
+        n = len(prompts)
+        if neg is None:
+            out = [[int(t) for t in ids if t != IMAGE_TOKEN_INDEX] for ids in prompts]
+        elif len(neg) and isinstance(neg[0], (list, tuple, np.ndarray)) or torch.is_tensor(neg) and neg.dim() == 2:
+            if len(neg) != n:
+                raise ValueError(f"guidance: {len(neg)} negative prompts for {n} requests")
+            out = [[int(t) for t in ids] for ids in neg]
+        else:
+            out = [[int(t) for t in neg] for _ in range(n)]
+        if any(len(ids) < 1 for ids in out):
+            raise ValueError("guidance: an empty negative prompt")
+        return out
+
+    def _negative_embeds(self, vis: torch.Tensor, neg_ids: Sequence[int]):
+        """A negative prompt's spliced prefix: markers it keeps take the SAME kept visual rows (no second ViT pass); without markers
+        it is a text-only splice (zero frames, zero visual rows)."""
+        if any(t == IMAGE_TOKEN_INDEX for t in neg_ids):
+            return self.project_splice(vis, neg_ids)
+        return self.text_embeds(neg_ids)
+
+    def text_embeds(self, ids: Sequence[int]):
+        """Text ids through the embedding table alone -> (embeds [L_pad, d] fp16, seq_len): the splice of a prompt without frames
+        (image markers among the ids are dropped, as `splice_rows` drops markers beyond the number of frames)."""
+        plan = self.splice_plan([int(t) for t in ids], 0, 0)
+        if plan["seq_len"] < 1:
+            raise ValueError("a prompt without text tokens")
+        none = torch.empty(0, 0, self.v["hidden_size"], dtype=torch.float16, device=self.dev)
+        return self.project_splice(none, plan=plan)
+
+    def _caption_batch_guided(self, clips, token_kept_ratio, max_new_tokens, eos_id, check_every, sampling, streams, share, logprobs,
+                              logit_rules, stop, attn_map, gd):
+        """`caption_batch` under guidance: every clip's prefix and its negative's, then `generate`.  Clips with equal non-None share
+        keys and equal shapes run the ViT once; their KV is not shared."""
+        B = len(clips)
+        GD.pair_slots(B, self.max_batch)
+        if share is not None and len(share) != B:
+            raise ValueError(f"{len(share)} share keys for {B} clips")
+        negs = self._negative_ids(gd, [ids for _, ids in clips])
+        vis_of, embs, lens, nemb = {}, [], [], []
+        for i, (px, ids) in enumerate(clips):
+            key = None if share is None or share[i] is None else (share[i], tuple(px.shape))
+            vis = vis_of.get(key) if key is not None else None
+            if vis is None:
+                vis = self.vit_encode(px, self.tome_r(token_kept_ratio, px.shape[-2], px.shape[-1]))
+                if key is not None:
+                    vis_of[key] = vis
+            emb, L = self.project_splice(vis, ids)
+            embs.append(emb)
+            lens.append(L)
+            nemb.append(self._negative_embeds(vis, negs[i]))
+        return self.generate(embs, lens, max_new_tokens, eos_id, check_every, sampling=sampling, streams=streams, logprobs=logprobs,
+                             logit_rules=logit_rules, **({} if stop is None else dict(stop=stop)),
+                             **({} if attn_map is None else dict(attn_map=attn_map)), guidance=dict(scale=gd["scale"], negative=nemb))
 
     def caption_ids(self, pixels: torch.Tensor, input_ids: Sequence[int], token_kept_ratio: float, max_new_tokens: int,
                     eos_id: Optional[int] = 2, sampling: Optional[dict] = None, stream: int = 0, logprobs: Optional[int] = None,
-                    logit_rules: Optional[dict] = None, stop: Optional[dict] = None, attn_map: Optional[dict] = None):
+                    logit_rules: Optional[dict] = None, stop: Optional[dict] = None, attn_map: Optional[dict] = None,
+                    guidance: Optional[dict] = None):
         """Whole path for one clip: the call sequence of inference.py:87-96.  sampling / stream / logprobs / logit_rules / stop /
-        attn_map: as in `generate`."""
+        attn_map: as in `generate`.  guidance=dict(scale=g, negative_ids=None | ids): as in `caption_batch`."""
+        gd = GD.check_guidance(guidance)
+        if gd is not None:
+            return self.caption_batch([(pixels, input_ids)], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling, streams=[stream],
+                                      logprobs=logprobs, logit_rules=logit_rules, stop=stop, attn_map=attn_map, guidance=gd)[0]
         check_logprobs(logprobs)
         if attn_map is not None:
             AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
@@ -1356,7 +1499,7 @@ class AuroraCapEngine:
     def caption_batch(self, clips: Sequence[Tuple[torch.Tensor, Sequence[int]]], token_kept_ratio: float, max_new_tokens: int,
                       eos_id: Optional[int] = 2, prefill_group: int = 8, check_every: int = 32, sampling: Optional[dict] = None,
                       streams: Optional[Sequence[int]] = None, share: Optional[Sequence] = None, logprobs: Optional[int] = None,
-                      logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
+                      logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None, guidance: Optional[dict] = None):
         """Whole path for up to max_batch clips at once: (pixel_values [f, C, H, W], input_ids with -200 markers) each.
         Clips may differ in frame count and prompt; neighbours whose spliced length is equal share one prefill pass - with
         `prompt_bucket`, neighbours whose lengths round up to the same multiple of the bucket (`prefill_groups`).
@@ -1371,7 +1514,14 @@ class AuroraCapEngine:
         logprobs=n: a dict per clip instead of its ids, as in `generate`.
         logit_rules: one dict for every clip of the call, as in `generate` (each clip's own generated tokens are its history).
         stop: one dict for every clip, or a list with one dict or None per clip, as in `generate`; siblings get theirs like any clip.
-        attn_map: as in `generate` - a dict per clip with its attn_map; keys=None is the longest spliced prompt rounded up to 64."""
+        attn_map: as in `generate` - a dict per clip with its attn_map; keys=None is the longest spliced prompt rounded up to 64.
+        guidance=dict(scale=g, negative_ids=None | ids | [ids, ...]): classifier-free guidance as in `generate`, at most
+        max_batch // 2 clips.  negative_ids None: each clip's own prompt without its image markers - a text-only prefix, the language
+        prior alone; a negative that keeps its markers is spliced over the clip's kept visual rows (no second ViT pass)."""
+        gd = GD.check_guidance(guidance)
+        if gd is not None:
+            return self._caption_batch_guided(clips, token_kept_ratio, max_new_tokens, eos_id, check_every, sampling, streams, share,
+                                              logprobs, logit_rules, stop, attn_map, gd)
         lpn = check_logprobs(logprobs)
         if attn_map is not None:
             AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
@@ -1464,11 +1614,13 @@ class AuroraCapEngine:
 
     def caption_prompts(self, pixels: torch.Tensor, list_of_input_ids: Sequence[Sequence[int]], token_kept_ratio: float, max_new_tokens: int,
                         eos_id: Optional[int] = 2, sampling: Optional[dict] = None, streams: Optional[Sequence[int]] = None,
-                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
+                        logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None,
+                        guidance: Optional[dict] = None):
         """One clip, several prompts: `caption_batch` over (pixels, ids) for every prompt with one share key, in chunks of max_batch
         (the ViT runs once per chunk).  Ids in prompt order, each what `caption_ids(pixels, ids)` gives.  logprobs / logit_rules: as
         in `generate`; stop: one dict for every prompt, or a list with one dict or None per prompt; attn_map: as in `caption_batch`,
-        per chunk."""
+        per chunk.  guidance: as in `caption_batch`, one negative for every prompt or one each; a chunk then holds max_batch // 2
+        prompts."""
         check_logprobs(logprobs)
         if attn_map is not None:
             AM.check_attn_map(attn_map, self.l["num_hidden_layers"])
@@ -1477,6 +1629,18 @@ class AuroraCapEngine:
         stops = None if stop is None else self._stop_records(stop, len(prompts), max_new_tokens)
         st = list(range(len(prompts))) if streams is None else [int(x) for x in streams]
         out: List[List[int]] = []
+        gd = GD.check_guidance(guidance)
+        if gd is not None:
+            negs = self._negative_ids(gd, prompts)
+            per = max(1, self.max_batch // 2)
+            GD.pair_slots(1, self.max_batch)
+            for c0 in range(0, len(prompts), per):
+                chunk = prompts[c0:c0 + per]
+                out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
+                                          streams=st[c0:c0 + len(chunk)], share=[0] * len(chunk), logprobs=logprobs,
+                                          logit_rules=logit_rules, attn_map=attn_map, stop=None if stops is None else stops[c0:c0 + len(chunk)],
+                                          guidance=dict(scale=gd["scale"], negative_ids=negs[c0:c0 + len(chunk)]))
+            return out
         for c0 in range(0, len(prompts), self.max_batch):
             chunk = prompts[c0:c0 + self.max_batch]
             out += self.caption_batch([(pixels, ids) for ids in chunk], token_kept_ratio, max_new_tokens, eos_id, sampling=sampling,
@@ -1511,7 +1675,7 @@ class AuroraCapEngine:
     def caption_stream(self, clips, token_kept_ratio: float, max_new_tokens: int, eos_id: Optional[int] = 2, slots: Optional[int] = None,
                        check_every: int = 16, on_error=None, overlap: Optional[bool] = None, front_cus: int = 16, front_graph: bool = True,
                        sampling: Optional[dict] = None, stream_of=None, share_key=None, logprobs: Optional[int] = None,
-                       logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
+                       logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None, guidance: Optional[dict] = None):
         """Continuous batching over an iterable of (pixel_values, input_ids): up to `slots` (default max_batch) captions are
         in flight; every `check_every` decode steps the finished slots are collected and re-filled with the next clips
         (ViT + projector + prefill into the free slot while the others keep their KV and state).  Yields (index, ids) in
@@ -1546,7 +1710,11 @@ class AuroraCapEngine:
         option is flipped when the call starts, since front-end graphs cannot be dropped while clips are staged behind them.
         attn_map: as in `generate` - yields (index, dict) with the clip's attn_map, the rows of a caption run alone, in both modes; a
         re-filled slot's rows are cleared where its length is.  keys=None: the engine's whole context rounded up to 64 (the prompts of
-        a stream differ)."""
+        a stream differ).
+        guidance: not in this call yet - a pair of slots would have to travel through the staged commit and the row exchange
+        together; a request (a scale other than None / 1) raises NotImplementedError."""
+        if GD.check_guidance(guidance) is not None:
+            raise NotImplementedError("caption_stream(guidance=...): guided requests go through generate / caption_ids / caption_batch / caption_prompts")
         lpn = check_logprobs(logprobs)
         samp = S.check_sampling(sampling)
         rules = LR.check_logit_rules(logit_rules)

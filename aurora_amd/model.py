@@ -21,6 +21,8 @@ import torch
 
 from .engine import AuroraCapEngine, splice_rows, tokens_at_layer
 from .logit_rules import KEYS as LOGIT_RULE_KEYS, check_logit_rules
+from . import guidance as GD
+from .guidance import pair_slots
 from . import stopping as ST
 from .sampling import DEFAULT_TOP_K, check_sampling
 from .scoring import check_logprobs
@@ -145,7 +147,7 @@ class _LLM:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
                  min_new_tokens: Optional[int] = None, stop_strings=None, tokenizer=None, stop_token_ids=None, merge_map=None,
                  merge_sizes=None, output_attentions: bool = False, attention_keys: Optional[int] = None, attention_layers=None,
-                 vis_rows=None, **unused):
+                 vis_rows=None, guidance_scale: Optional[float] = None, negative_prompt_ids=None, negative_inputs_embeds=None, **unused):
         """`merge_map` / `merge_sizes` (what `AuroraModel.forward` adds with data["output_merge_map"]) are accepted and ignored, so
         `generate(**out, ...)` keeps working.
         output_attentions=True (transformers' flag; needs return_dict_in_generate=True, ValueError otherwise): the result carries
@@ -172,7 +174,16 @@ class _LLM:
         stop_strings=[...] with tokenizer=tok (transformers requires the tokenizer too; without it: ValueError): generation ends
         behind the token whose text completes one of the strings, which stays in the output, as with transformers'
         StopStringCriteria (`aurora_amd.stopping`).  eos_token_id may be a list: its first id is the EOS, the others - and
-        stop_token_ids - end the generation the same way, but `min_new_tokens` holds back the first alone."""
+        stop_token_ids - end the generation the same way, but `min_new_tokens` holds back the first alone.
+        guidance_scale (None or 1 = off) with negative_prompt_ids (text ids, [n] or [1, n], through the embedding table) or
+        negative_inputs_embeds ([1, n, d]): transformers' classifier-free guidance (`aurora_amd.guidance`), the first processor ahead
+        of the three above - every pick contrasts the prompt's distribution with the negative prompt's, which decodes in a second
+        KV slot (an engine with max_batch >= 2).  transformers falls back to the prompt's last token when no negative is given; with
+        inputs_embeds there is none, so a scale without a negative raises ValueError.  Log-probabilities stay those of the model's
+        conditional row."""
+        gscale = GD.check_scale(guidance_scale)
+        if gscale is not None and negative_prompt_ids is None and negative_inputs_embeds is None:
+            raise ValueError("guidance_scale needs negative_prompt_ids or negative_inputs_embeds: the prompt is embeddings, so there is no default negative prompt")
         if stop_strings is not None and tokenizer is None:
             raise ValueError("stop_strings needs tokenizer= as well: the strings are matched on the text the tokens decode to")
         if output_logprobs and not return_dict_in_generate:
@@ -211,6 +222,18 @@ class _LLM:
             kw["stop"] = stop
         if am is not None:
             kw["attn_map"] = am
+        if gscale is not None:
+            if negative_inputs_embeds is not None:
+                ne = negative_inputs_embeds
+                if ne.dim() != 3 or ne.shape[0] != 1 or ne.shape[2] != d or ne.shape[1] < 1:
+                    raise ValueError(f"negative_inputs_embeds must be [1, n, {d}], got {tuple(ne.shape)}")
+                Ln = ne.shape[1]
+                npad = torch.zeros((Ln + 31) // 32 * 32, d, dtype=torch.float16, device=self._e.dev)
+                npad[:Ln] = ne[0].to(device=self._e.dev, dtype=torch.float16)
+            else:
+                nids = negative_prompt_ids.reshape(-1).tolist() if torch.is_tensor(negative_prompt_ids) else [int(t) for t in np.asarray(negative_prompt_ids).reshape(-1)]
+                npad, Ln = self._e.text_embeds(nids)
+            kw["guidance"] = dict(scale=gscale, negative=[(npad, Ln)])
         if lpn is None and am is None:
             ids = self._e.generate([pad], [L], n, eos_id=eos, **kw)[0]
             seq = torch.tensor([ids], dtype=torch.long)
@@ -249,7 +272,8 @@ class AuroraModel:
         return model
 
     def caption_batch(self, clips, max_new_tokens: int = 2048, eos_token_id="default", sampling=None, streams=None, share=None,
-                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None):
+                      logprobs: Optional[int] = None, logit_rules: Optional[dict] = None, stop=None, attn_map: Optional[dict] = None,
+                      guidance_scale: Optional[float] = None, negative_prompt=None, tokenizer=None):
         """Several clips through the three calls at once (what a harness gets by looping inference.py:87-96 over its
         requests): clips = [(pixel_values [f, c, h, w], input_ids with -200 markers), ...] -> list of new-token id lists,
         identical per clip to the one-at-a-time calls.  Uses visual_encoder.visual_token_merge_ratio.
@@ -262,7 +286,11 @@ class AuroraModel:
         stop=dict(token_ids=(), strings=(), max_new_tokens=0) for every clip, or a list with one dict or None per clip: stop ids,
         stop strings (`llm.use_tokenizer(tok)` first) and a budget of the clip's own (AuroraCapEngine.generate).
         attn_map=dict(keys=W or None, layers=None or a list): a dict per clip that also holds attn_map float32 [n, W]
-        (AuroraCapEngine.generate), visual_attention [n, nvis] - its columns at the clip's visual tokens - and visual_share [n]."""
+        (AuroraCapEngine.generate), visual_attention [n, nvis] - its columns at the clip's visual tokens - and visual_share [n].
+        guidance_scale (None or 1 = off): classifier-free guidance for every clip (AuroraCapEngine.caption_batch); negative_prompt
+        None: each clip's own prompt without its frames; a text (with tokenizer=, or the one `llm.use_tokenizer` got) or its input
+        ids: that prompt for every clip.  A chunk then holds max_batch // 2 clips."""
+        gd = self._guidance(guidance_scale, negative_prompt, tokenizer)
         check_logprobs(logprobs)
         if attn_map is not None:
             AM.check_attn_map(attn_map, self.llm.config["num_hidden_layers"])
@@ -270,6 +298,9 @@ class AuroraModel:
         eos = self.llm.eos_token_id if eos_token_id == "default" else eos_token_id
         out = []
         B = self.engine.max_batch
+        if gd is not None:
+            pair_slots(1, B)
+            B //= 2
         n = min(max_new_tokens, self.engine.max_new_tokens)
         if stop is not None and not isinstance(stop, dict):
             stop = list(stop)
@@ -289,12 +320,30 @@ class AuroraModel:
                 kw["stop"] = stop if isinstance(stop, dict) else stop[c0:c0 + len(group)]
             if attn_map is not None:
                 kw["attn_map"] = attn_map
+            if gd is not None:
+                kw["guidance"] = gd
             res = self.engine.caption_batch(group, self.visual_encoder.visual_token_merge_ratio, n, eos, **kw)
             if attn_map is not None:
                 for (px, ids), r in zip(group, res):
                     self._add_visual(r, px.shape, ids)
             out.extend(res)
         return out
+
+    def _guidance(self, guidance_scale, negative_prompt, tokenizer=None) -> Optional[dict]:
+        """guidance_scale / negative_prompt of a caption call -> the engine's `guidance=` dict, or None (no request)"""
+        g = GD.check_scale(guidance_scale)
+        if g is None:
+            return None
+        if self.slowfast:
+            raise NotImplementedError("guidance on a slow-fast model (ragged per-frame token counts)")
+        if isinstance(negative_prompt, str):
+            tok = tokenizer if tokenizer is not None else self.llm._stop_tokenizer
+            if tok is None:
+                raise ValueError("negative_prompt as text needs tokenizer= (or llm.use_tokenizer(tok) earlier); pass its input ids otherwise")
+            negative_prompt = tok(negative_prompt).input_ids
+        if negative_prompt is not None:
+            negative_prompt = negative_prompt.reshape(-1).tolist() if torch.is_tensor(negative_prompt) else [int(t) for t in negative_prompt]
+        return dict(scale=g, negative_ids=negative_prompt)
 
     def _add_visual(self, r: dict, shape, ids):
         """visual_attention [n, nvis] and visual_share [n] beside a result's attn_map: its columns at the context positions of the
@@ -317,13 +366,16 @@ class AuroraModel:
                                                self.visual_encoder.visual_token_merge_ratio, share=share)
 
     def caption_prompts(self, pixel_values, list_of_input_ids, max_new_tokens: int = 2048, eos_token_id="default", sampling=None,
-                        streams=None, logit_rules: Optional[dict] = None, stop=None):
+                        streams=None, logit_rules: Optional[dict] = None, stop=None, guidance_scale: Optional[float] = None,
+                        negative_prompt=None, tokenizer=None):
         """One clip, several prompts (the five VDC questions about a video): pixel_values [f, c, h, w], each prompt's input ids with
         -200 markers -> one new-token id list per prompt, in order, each identical to captioning (clip, prompt) alone.  The ViT runs
         once per chunk of max_batch prompts and the later prompts prefill only the rows behind the last visual token.  A slow-fast
         model never shares: its prompts run one at a time through the three calls.  logit_rules / stop: as in `caption_batch`
-        (a slow-fast model takes no stop records)."""
+        (a slow-fast model takes no stop records).  guidance_scale / negative_prompt / tokenizer: as in `caption_batch`; the ViT
+        still runs once per chunk, the prompts' KV is not shared."""
         rules = check_logit_rules(logit_rules)
+        self._guidance(guidance_scale, negative_prompt, tokenizer)
         prompts = [ids.tolist() if torch.is_tensor(ids) else list(ids) for ids in list_of_input_ids]
         if self.slowfast and stop is not None:
             raise NotImplementedError("caption_prompts(stop=) on a slow-fast model")
@@ -339,7 +391,8 @@ class AuroraModel:
             return out
         return self.caption_batch([(pixel_values, ids) for ids in prompts], max_new_tokens, eos_token_id, sampling, streams,
                                   share=[0] * len(prompts), **({} if rules is None else dict(logit_rules=rules)),
-                                  **({} if stop is None else dict(stop=stop)))
+                                  **({} if stop is None else dict(stop=stop)),
+                                  **({} if guidance_scale is None else dict(guidance_scale=guidance_scale, negative_prompt=negative_prompt, tokenizer=tokenizer)))
 
     def caption_stream(self, clips, max_new_tokens: int = 2048, eos_token_id="default", check_every: int = 16, on_error=None,
                        overlap=None, sampling=None, stream_of=None, share_key=None, logit_rules: Optional[dict] = None, stop=None,

@@ -252,6 +252,23 @@ typedef struct aur_logit_rules { float repetition_penalty; int32_t no_repeat_ngr
  * aur_begin_batch and aur_slot_reset set the slots they clear to neutral (the all-zero record: a penalty <= 0 counts as 1, like
  * (1, 0, 0)): such a slot's row is never touched.  A commit keeps a slot's record. */
 int aur_slot_logit_rules(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_logit_rules* rules_dev, void* stream);
+/* Classifier-free guidance: with option "guidance" = 1 (aur_set_option) a guided request is a PAIR of slots that
+ * decode in lock-step.  The leader's record names its partner, whose sequence is the negative prompt; the partner's own record stays
+ * neutral.  Ahead of every prefill's / commit's / decode step's pick - and ahead of the logit rules - the leader's fp32 row c becomes
+ *   out_i = scale * (lc_i - lu_i) + lu_i,  lc = log_softmax(c), lu = log_softmax(u), u = the partner's row
+ * (transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor; aurora_amd/guidance.py is the definition in numpy), and behind the
+ * pick the model's row is back, so aur_copy_logits and the log-probability records keep seeing the unmodified conditional row.  Behind
+ * the stop check the partner takes the leader's newest token, out_len, finished flag and next input: both sequences hold the same
+ * generated ids and stop together.  A first pick needs the partner's row: prefill the partner before its leader.
+ * scale: finite, positive and not 1 asks for guidance; anything else - the all-zero record among them - is neutral: the slot is not
+ * touched.  partner: a slot of the bank, clamped into [0, max_batch) by the kernels. */
+typedef struct aur_guidance { float scale; int32_t partner; } aur_guidance;
+/* per-slot records of the selected bank: aur_slot_sampling's contract - device-to-device from caller-owned DEVICE memory, enqueue-only,
+ * recordable; a capture freezes the pointer, not the values; ordered before the prefill / commit that picks the slot's first token.
+ * aur_begin_batch and aur_slot_reset set the slots they clear to neutral, and a leader whose partner they clear as well; a commit keeps
+ * a slot's record.  The records and the save buffer (max_batch * llm_vocab * 4 bytes per bank) live in memory the first "guidance" 1
+ * allocates (aur_workspace_bytes does not grow): AUR_ERR_STATE before that. */
+int aur_slot_guidance(aur_ctx* ctx, int32_t slot0, int32_t nslots, const aur_guidance* recs_dev, void* stream);
 /* Stop conditions behind the pick: with option "stop_rules" = 1 (aur_set_option) stop_check_kernel runs behind
  * every prefill's / commit's / decode step's pick, greedy or sampled, eager or captured, and sets finished[b] of an unfinished slot whose
  * newest token t = h[n - 1] (h = the n tokens the slot has GENERATED, never the prompt) fulfils one of
@@ -474,6 +491,12 @@ int aur_sample_rows(aur_ctx* ctx, const float* logits, int32_t rows, int32_t voc
  * its input again.  Allocates its side list, synchronises the stream and frees it: not recordable. */
 int aur_logit_rules_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const int32_t* ids_dev, int32_t ids_stride,
                          const int32_t* lens_dev, const aur_logit_rules* rules_dev, int32_t eos_id, int32_t restore, void* stream);
+/* The guidance kernels alone on a caller's buffer (parity tests): logits fp32 [rows, vocab], read and written; recs_dev [rows], whose
+ * partners are rows of the same buffer (clamped into [0, rows)); save fp32 [rows, vocab].  mode 0: guidance_apply_kernel - a leader's
+ * row goes into its save row and the guided row stands in its place; every other row, and every other save row, is not touched.
+ * mode 1: guidance_restore_kernel - the leaders' save rows back.  Enqueue-only. */
+int aur_guidance_rows(aur_ctx* ctx, float* logits, int32_t rows, int32_t vocab, const aur_guidance* recs_dev, float* save, int32_t mode,
+                      void* stream);
 /* stop_check_kernel alone on caller rows (parity tests).  ids_dev int32 [rows, ids_stride] and lens_dev int32 [rows]: row i's generated
  * tokens are ids_dev[i][0 .. min(lens_dev[i], ids_stride)); rules_dev [rows] (8-byte aligned); finished_dev int32 [rows], read and written:
  * a row whose flag is set is skipped, a row that stops gets 1; batch_max_new: the limit a record with max_new_tokens <= 0 stands for
@@ -579,7 +602,9 @@ int aur_attn_map_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, con
  * row in LDS when it fits) / 0 (re-reads it from L2; same tokens), "logit_rules" 0 (default: the launches are exactly those of a ctx
  * that never heard of them) / 1 (logit_rules_apply_kernel ahead of every pick and logit_rules_restore_kernel behind it, with the slots'
  * aur_logit_rules records; frozen inside captured graphs exactly like "sampling"; the first 1 allocates the banks' side lists -
- * max_batch * (max_new_tokens + 1) entries of 8 bytes each - which live as long as the ctx), "stop_rules" 0 (default: the launches are exactly those of a ctx that never
+ * max_batch * (max_new_tokens + 1) entries of 8 bytes each - which live as long as the ctx), "guidance" 0 (default: the launches are exactly those of a ctx that never heard of it) / 1 (guidance_apply_kernel ahead of the logit rules,
+ * guidance_restore_kernel behind the pick and guidance_follow_kernel behind the stop check, with the slots' aur_guidance records; frozen inside captured graphs exactly like
+ * "sampling"; the first 1 allocates the banks' records and save buffers - max_batch * llm_vocab * 4 bytes each - which live as long as the ctx), "stop_rules" 0 (default: the launches are exactly those of a ctx that never
  * heard of it) / 1 (stop_check_kernel behind every pick, with the slots' aur_stop_rules records; frozen inside captured graphs exactly like
  * "sampling"; the first 1 allocates the banks' records - max_batch * sizeof(aur_stop_rules) each - which live as long as the ctx).  Keep the graphs: "tome_fused_ln" 1 (default: LayerNorm 2 of a merging ViT layer comes out of the ToMe merge
  * launch) / 0 (its own launch; bitwise the same); "prefill_prune_last" 1 (default) / 0: the last layer of a prefill computes K / V for
@@ -597,7 +622,7 @@ int aur_attn_map_rows(aur_ctx* ctx, const void* x, int32_t rows, int32_t kx, con
  * LDS above; mk_skinny in aurora_amd/csrc/engine.hip is the one place that picks it, for the step, aur_microbench and the parity entries), the 256x256 GEMM always takes the LDS-transposed epilogue and the compact tile order, residual projections run 8 waves. */
 int aur_set_option(aur_ctx* ctx, const char* name, int64_t value);
 /* Time one kernel of the LLM path in isolation on the current generation state (after aur_llm_prefill):
- * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), dec_stop (stop_check_kernel; option "stop_rules" 1), pre_norm, pre_qkv, pre_attn,
+ * kernel in {dec_norm, dec_qkv, dec_attn, dec_o, dec_gateup, dec_down, dec_lm_head, dec_pick (the token pick of the current "sampling" mode), dec_rules (the logit-rule apply + restore pair; option "logit_rules" 1), dec_guid (guidance's apply + restore + follow; option "guidance" 1), dec_stop (stop_check_kernel; option "stop_rules" 1), pre_norm, pre_qkv, pre_attn,
  * pre_o, pre_gateup, pre_down}; mean microseconds per launch over `iters` launches cycling through the layers. */
 int aur_microbench(aur_ctx* ctx, const char* kernel, int32_t iters, double* us_out, void* stream);
 

@@ -45,6 +45,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--repetition_penalty', type=float, default=None, help='divide (positive) / multiply (negative) the logit of every token generated so far by this (> 0; 1.0 = off)')
     parser.add_argument('--no_repeat_ngram_size', type=int, default=None, help='no n-gram of this size occurs twice in the generated tokens (0 = off)')
     parser.add_argument('--min_new_tokens', type=int, default=None, help='the EOS token cannot be picked before this many tokens (0 = off)')
+    # classifier-free guidance (aurora_amd.guidance): every pick contrasts the prompt with a negative prompt that decodes beside it
+    parser.add_argument('--guidance_scale', type=float, default=None, metavar='G',
+                        help='contrast the caption\'s distribution with a negative prompt\'s: G * (log p - log p_neg) + log p_neg ahead of every '
+                             'pick (> 0; 1.0 = off; above 1 pushes down what the language prior alone would have written)')
+    parser.add_argument('--negative_prompt', default=None, metavar='TEXT',
+                        help='with --guidance_scale: the negative prompt (default: --prompt without the visual input); with --synthetic there is '
+                             'no tokenizer: the text is ignored and the default negative is used')
     # more questions about the same input: the vision tower runs once and the later prompts prefill only the rows behind the last visual token
     parser.add_argument('--stop', action='append', default=[], metavar='STR',
                         help='end the caption behind the token that completes this text (repeatable, at most 8 of up to 64 bytes); the text '
@@ -150,6 +157,13 @@ def main():
     except ValueError as e:
         sys.exit(f"error: {e}")
     try:
+        from aurora_amd.guidance import check_scale
+        gscale = check_scale(args.guidance_scale)
+    except ValueError as e:
+        sys.exit(f"error: {e}")
+    if gscale is not None and args.score is not None:
+        sys.exit("error: --guidance_scale goes with generated captions (not with --score)")
+    try:
         from aurora_amd.stopping import check_stop
         stop = check_stop(dict(strings=args.stop, token_ids=args.stop_token_id), need_table=False)
     except ValueError as e:
@@ -169,7 +183,7 @@ def main():
         cfg = S.AURORACAP_7B
         w = {"vit": S.vit_weights(cfg["vit"]), "projector": S.projector_weights(1280, 4096), "llm": S.llm_weights(cfg["llm"])}
         n_prompts = 1 + len(args.extra_prompt)
-        eng = AuroraCapEngine(cfg, w, max_frames=args.num_frm, max_batch=n_prompts,
+        eng = AuroraCapEngine(cfg, w, max_frames=args.num_frm, max_batch=n_prompts * (2 if gscale is not None else 1),
                               max_ctx=30 + args.num_frm * 729 + args.max_new_tokens + 64 + 3 * len(args.extra_prompt),
                               max_new_tokens=args.max_new_tokens)
         model = AuroraModel(eng, eos_token_id=None)
@@ -224,9 +238,12 @@ def main():
         per_frame = (image_size // patch) ** 2                                      # upper bound: token_kept_ratio = 1.0 keeps all patches
         max_ctx = -(-(n_text + n_img * per_frame + args.max_new_tokens) // 64) * 64
         model = AuroraModel.from_pretrained(args.model_path, max_frames=max(n_img, 1), max_ctx=max_ctx,
-                                            max_new_tokens=args.max_new_tokens, max_batch=1 + len(extra_ids))
+                                            max_new_tokens=args.max_new_tokens, max_batch=(1 + len(extra_ids)) * (2 if gscale is not None else 1))
 
     model.visual_encoder.reset_tome_r(args.token_kept_ratio)
+    neg_ids = None                    # the negative prompt's text ids; None = the prompt itself without its image markers
+    if gscale is not None and args.negative_prompt is not None and tokenizer is not None:
+        neg_ids = [t for t in process_text(build_prompt(args.negative_prompt, 0), tokenizer)[0].tolist() if t != -200]
     if args.score is not None:        # how likely is this answer: one pass over prompt + answer, the answer's rows scored
         px = data["pixel_values"][0] if data["pixel_values"].dim() == 5 else data["pixel_values"]
         ctx_ids = data["input_ids"][0].tolist()
@@ -244,7 +261,8 @@ def main():
         if args.stop:
             model.llm.use_tokenizer(tokenizer)
         outs = model.caption_prompts(px, [data["input_ids"][0].tolist()] + extra_ids, max_new_tokens=args.max_new_tokens, sampling=samp,
-                                     **(dict(logit_rules=rule_args) if rule_args else {}), **(dict(stop=stop) if stop is not None else {}))
+                                     **(dict(logit_rules=rule_args) if rule_args else {}), **(dict(stop=stop) if stop is not None else {}),
+                                     **(dict(guidance_scale=gscale, negative_prompt=neg_ids) if gscale is not None else {}))
         for ids in outs:
             print(ids if tokenizer is None else tokenizer.batch_decode([ids], skip_special_tokens=True)[0])
         return
@@ -262,7 +280,9 @@ def main():
                               **(dict(stop_token_ids=args.stop_token_id) if args.stop_token_id else {}),
                               **(dict(return_dict_in_generate=True) if args.logprobs is not None or want_attn else {}),
                               **(dict(output_logprobs=True, top_logprobs=args.logprobs) if args.logprobs is not None else {}),
-                              **(dict(output_attentions=True) if want_attn else {}))
+                              **(dict(output_attentions=True) if want_attn else {}),
+                              **(dict(guidance_scale=gscale, negative_prompt_ids=neg_ids if neg_ids is not None
+                                      else [t for t in data["input_ids"][0].tolist() if t != -200]) if gscale is not None else {}))
     lp_out = None
     if want_attn:
         write_attn_outputs(args, cont, output)
